@@ -33,7 +33,20 @@ Metric: "NTT 2^24 field-elems/sec + FRI commit ms; % HBM roofline".
   * cpu_baseline: the oracle's C restatement of the reference NTT
     (oracle/liboracle.so, 1 thread) on one 2^24 NTT, rank 0 at N = 1 only.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run (no --full) sets up, warms up, times the K steps and prints the
+headline line: value, ms_per_step, the roofline of the dominant kernel (timed
+live inside the K steps) and, at N > 1, the pre-flight record.  Everything
+that takes a run of its own -- the extras, configs 4 and 5, strong scaling,
+the in-run output checks against a single-GPU recompute, the committed VALU
+profile reading and the CPU baselines -- is behind --full.
+
+--dump-outputs DIR writes what the last timed step computed (the output
+vector of the headline NTT, this rank's shard at N > 1) as float64 .npy files:
+a seeded sample of elements with their indices, and per-block limb sums over
+the whole vector (dump_outputs).  The input is seeded, so two builds run with
+the same arguments can be compared file for file.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       torchrun --nproc-per-node N bench.py --gpus N ...  (one rank per GPU)
 """
 import argparse
@@ -342,6 +355,39 @@ def load_valu_profile():
     return out
 
 
+DUMP_SAMPLE = 1 << 20  # elements of the output kept by --dump-outputs (32 MB as float64 limbs)
+DUMP_BLOCKS = 1 << 12  # blocks of the whole-vector limb sums
+
+
+def dump_outputs(dirname, name, t):
+    """--dump-outputs: the (n, 4) int32 limb tensor `t` as float64 arrays (a
+    u32 limb is exact in a double) under `dirname`:
+      <name>.npy             the elements at <name>_index.npy, (s, 4) limbs,
+                             little-endian; the whole vector when n <= DUMP_SAMPLE;
+      <name>_index.npy       the s sampled indices (fixed seed, sorted);
+      <name>_block_sums.npy  (b, 4): per limb, the sum over each of b equal
+                             contiguous blocks of the WHOLE vector (exact:
+                             at most 2^16 x 2^32 per sum), so an element
+                             outside the sample still shows.
+    At most 8 x 5 x DUMP_SAMPLE bytes + the sums: ~40 MB."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    n = t.shape[0]
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0x5EED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+    else:
+        idx = np.arange(n, dtype=np.int64)
+    sample = t.index_select(0, torch.from_numpy(idx).to(t.device)).cpu().numpy().view(np.uint32)
+    blocks = min(n, max(DUMP_BLOCKS, n >> 16))
+    limbs = t.to(torch.int64) & 0xFFFFFFFF
+    sums = limbs.reshape(blocks, n // blocks, 4).sum(1).cpu().numpy()
+    np.save(os.path.join(dirname, name + ".npy"), sample.astype(np.float64))
+    np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, name + "_block_sums.npy"), sums.astype(np.float64))
+
+
 def load_pmc(kernel, log_n):
     """HBM traffic per launch from the committed rocprofv3 PMC summary, if it
     matches this kernel/size (tools/pmc_summary.py writes it)."""
@@ -367,9 +413,15 @@ def main():
     ap.add_argument("--prof-every", type=int, default=8,
                     help="HIP-event kernel timer on every k-th step of the timed region (each "
                          "timing event costs the stream a few us; 1 = every step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the secondary timings (extras, configs 4 and 5, strong "
+                         "scaling), the in-run output checks, the committed VALU profile reading and "
+                         "the CPU baselines; off: the headline measurement only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output to DIR/*.npy (dump_outputs)")
     ap.add_argument("--extra-reps", type=int, default=3, help="reps of the secondary timings")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary timings")
     ap.add_argument("--extras-budget-s", type=float, default=240.0,
                     help="watchdog on the secondary timings (0: off)")
     ap.add_argument("--headline-budget-s", type=float, default=180.0,
@@ -385,6 +437,9 @@ def main():
     ap.add_argument("--strong-log", type=int, default=28,
                     help="strong-scaling NTT size (log2), fixed over N; 0: off")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extras
 
     import torch
 
@@ -490,6 +545,9 @@ def main():
     if dist is not None:
         elapsed = _allreduce_max(elapsed)
     barrier()
+    if args.dump_outputs:  # before anything below reuses the buffers
+        last = batch.outs[(args.steps - 1) & 1] if sharded else out
+        dump_outputs(args.dump_outputs, "ntt_out" if world == 1 else "ntt_out_rank%d" % rank, last)
 
     if hw:
         hw.phase("headline_checks")
@@ -541,6 +599,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": ms_per_step,
         "higher_is_better": True,
         "scaling": "weak",
@@ -597,7 +656,7 @@ def main():
             "peak_rule": "one wave64 VALU instruction per 4 cycles per SIMD at 2.4 GHz",
             "source": "SQ_INSTS_VALU per launch (%s) x 64 lanes / live avg launch time" % valu[1],
         }
-    vp = load_valu_profile() if log_n == 24 else None
+    vp = load_valu_profile() if args.full and log_n == 24 else None
     if vp:
         result["valu_profile"] = vp
     if world > 1:
@@ -610,12 +669,13 @@ def main():
             result["sharded_phases"] = sharded_phases(kernels, log_n, log_p, passes)
             result["sharded_algorithm"] = batch.algorithm
             result["sharded_output_block_log"] = batch.log_s if batch.fused else log_n - log_p
-            try:
-                result["sharded_ntt_verified"] = sharded_ntt_check(batch, log_n, log_p, rank, world,
-                                                                   local)
-            except Exception as e:  # keep the headline line; report the failure
-                result["sharded_ntt_verified"] = False
-                result["sharded_ntt_check_error"] = "%s: %s" % (type(e).__name__, e)
+            if args.full:
+                try:
+                    result["sharded_ntt_verified"] = sharded_ntt_check(batch, log_n, log_p, rank, world,
+                                                                       local)
+                except Exception as e:  # keep the headline line; report the failure
+                    result["sharded_ntt_verified"] = False
+                    result["sharded_ntt_check_error"] = "%s: %s" % (type(e).__name__, e)
 
     if preflight is not None:
         result["preflight"] = preflight
@@ -625,9 +685,9 @@ def main():
     # inside a sharded prove leaves the others waiting in RCCL), every rank's
     # watchdog prints the headline line measured above and ends the process, so
     # the driver still gets the K-step measurement.
-    watchdog = _ExtrasWatchdog(result, rank, args.extras_budget_s)
+    watchdog = _ExtrasWatchdog(result, rank, args.extras_budget_s if args.full else 0)
 
-    if not args.no_extras and world == 1:
+    if extras and world == 1:
         reps = args.extra_reps
         # inverse NTT (out = NTT(x), so x is rewritten with itself); one
         # untimed call builds the inverse twiddle tables
@@ -807,7 +867,7 @@ def main():
         except Exception as e:  # keep the headline line; report the failure
             result["reference_test_points_error"] = "%s: %s" % (type(e).__name__, e)
 
-    if not args.no_extras and args.fri_log:
+    if extras and args.fri_log:
         try:
             result.update(config5(args, lib, ctx, local, world, rank, barrier))
         except Exception as e:  # keep the headline line; report the failure
@@ -823,7 +883,7 @@ def main():
                 result["replicas_ntt"] = replicas_ntt_extra(args, ntt_local, world, barrier, log_n)
             except Exception as e:
                 result["replicas_ntt_error"] = "%s: %s" % (type(e).__name__, e)
-    if not args.no_extras and args.strong_log:
+    if extras and args.strong_log:
         try:
             result["strong_ntt"] = strong_ntt(args, lib, ctx, local, world, rank, barrier)
         except Exception as e:
@@ -834,14 +894,14 @@ def main():
             except Exception as e:
                 result["config4_sharded_error"] = "%s: %s" % (type(e).__name__, e)
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(log_n)
         try:
             result["cpu_baseline_all_cores"] = cpu_baseline_all_cores(log_n)
         except Exception as e:  # the 1-core baseline stays the reported one
             result["cpu_baseline_all_cores"] = {"error": str(e)}
         result["vs_cpu_1core"] = value / result["cpu_baseline"]["value"]
-        if not args.no_extras and result.get("fri_commit_ms"):
+        if extras and result.get("fri_commit_ms"):
             try:
                 cf = cpu_baseline_fri_commit(log_n)
                 result["cpu_baseline_fri_commit"] = cf

@@ -170,3 +170,36 @@ def test_headline_watchdog_ends_a_stalled_gloo_collective_world2(tmp_path):
     d = json.loads(lines[0])
     assert d["phase"] == "preflight" and "did not finish" in d["headline_error"]
     assert "not reached" not in p.stdout
+
+
+def test_dump_outputs_sample_index_and_block_sums(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): float64 files, limbs exact, the
+    sample taken at the stored (seeded, sorted, repeatable) indices, and the
+    block sums covering every element of the vector."""
+    import numpy as np
+    import torch
+
+    import bench
+    from multilinear_amd import device as D
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 256)
+    monkeypatch.setattr(bench, "DUMP_BLOCKS", 16)
+    limbs = D.random_limbs(4096, 11)
+    limbs[0] = 0xFFFFFFFF  # the largest limb value survives the int32 view
+    t = torch.from_numpy(limbs.view(np.int32).copy())
+    for d, v in (("a", t), ("b", t), ("small", t[:64])):
+        bench.dump_outputs(str(tmp_path / d), "ntt_out", v)
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(a) == ["ntt_out.npy", "ntt_out_block_sums.npy", "ntt_out_index.npy"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    for f, v in a.items():  # same arguments, same files
+        assert np.array_equal(v, np.load(tmp_path / "b" / f))
+    idx = a["ntt_out_index.npy"].astype(np.int64)
+    assert idx.shape == (256,) and np.all(np.diff(idx) >= 0) and idx.min() >= 0 and idx.max() < 4096
+    assert np.array_equal(a["ntt_out.npy"], limbs[idx].astype(np.float64))
+    want = limbs.astype(np.uint64).reshape(16, 256, 4).sum(1)
+    assert np.array_equal(a["ntt_out_block_sums.npy"], want.astype(np.float64))
+    # a vector no longer than the sample is written whole
+    assert np.array_equal(np.load(tmp_path / "small" / "ntt_out.npy"), limbs[:64].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "small" / "ntt_out_index.npy"), np.arange(64.0))
+    assert np.load(tmp_path / "small" / "ntt_out_block_sums.npy").shape == (16, 4)

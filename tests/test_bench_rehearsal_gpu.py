@@ -33,7 +33,7 @@ def _run(extra_env, args, timeout, nproc=2):
 
 
 def test_rehearsal_n2_line_certifies_itself():
-    p, lines, _ = _run({}, ["--log-n", "20", "--steps", "3", "--warmup", "1", "--no-extras",
+    p, lines, _ = _run({}, ["--log-n", "20", "--steps", "3", "--warmup", "1", "--full", "--no-extras",
                             "--spinup-s", "0"], 110)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout + p.stderr[-2000:]
@@ -74,7 +74,7 @@ def test_rehearsal_extras_certify_against_single_gpu(nproc, corrupt):
     loops (MLH_BENCH_TEST_CORRUPT_SHARD) every bit is false and the line is
     still printed."""
     env = {} if corrupt is None else {"MLH_BENCH_TEST_CORRUPT_SHARD": corrupt}
-    p, lines, _ = _run(env, ["--log-n", "16", "--steps", "3", "--warmup", "1", "--spinup-s", "0",
+    p, lines, _ = _run(env, ["--log-n", "16", "--steps", "3", "--warmup", "1", "--spinup-s", "0", "--full",
                              "--no-cpu", "--fri-log", "20", "--strong-log", "20", "--extra-reps", "1"],
                        300, nproc)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -2,7 +2,8 @@
 # share cuda:0 and exchange through gloo (the script's logic, not a result).
 set -o pipefail
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+OUT=${OUT:-prof_out}  # output directory, relative to the repository root
+mkdir -p $OUT
 export MLH_BENCH_BACKEND=gloo
-timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu > gpurun_out/n2_bench.json 2> gpurun_out/n2_bench.err || { tail -30 gpurun_out/n2_bench.err; exit 1; }
-cat gpurun_out/n2_bench.json
+timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 5 --warmup 2 --no-cpu > $OUT/n2_bench.json 2> $OUT/n2_bench.err || { tail -30 $OUT/n2_bench.err; exit 1; }
+cat $OUT/n2_bench.json
