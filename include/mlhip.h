@@ -502,6 +502,111 @@ mlh_status mlh_sumcheck_prove_eq(mlh_ctx* ctx, const void* dev_evals, void* dev_
                                  const uint8_t sum[16], mlh_transcript* tr, uint8_t* polys_out,
                                  uint8_t* rs_out, uint8_t* delta_out);
 
+/* ---- constraint-system sumcheck (src/constraint_system) ------------------- *
+ * The general prover of constraint_system/sumcheck.rs: a row-major
+ * 2^log_height x width trace (element (i, j) at i*width + j), a delta table of
+ * 2^log_height elements (System::build_tables, :22-38: mlh_eq_table of the row
+ * challenges) and a composition sum_c mask[c] * constraint_c(row, randoms)
+ * (ConstraintSet::evaluate, evaluation.rs:21-29) of degree `degree`.
+ *
+ * A constraint program replaces Expr<F>(fn(&[F], &[F]) -> F)
+ * (constraints.rs:3-10): straight-line code over field elements, built on the
+ * host and interpreted on the device.  Wire format, little-endian, no padding:
+ *   header   7 x u32: width, n_randoms, n_consts, n_temps, n_instr,
+ *            n_constraints, degree
+ *   consts   n_consts x 16 bytes, canonical elements
+ *   code     n_instr x 8 bytes: op, dst_temp, a.kind, a.index, b.kind,
+ *            b.index, 0, 0   (op: 0 ADD, 1 SUB, 2 MUL, 3 NEG; temp[dst] =
+ *            a op b; NEG: temp[dst] = -a and b = (0, 0))
+ *   outputs  n_constraints x 2 bytes: kind, index (constraint c's value)
+ * An operand is (kind, index): kind 0 column (the row's element `index`),
+ * 1 random, 2 const, 3 temp.  Limits: width 1..32, n_temps <= 32,
+ * n_consts <= 64, n_randoms <= 64, n_constraints 1..256, n_instr <= 4096,
+ * degree 1..7.  mlh_cs_program_create returns MLH_ERR_INVALID for a buffer
+ * that is truncated or has trailing bytes, an index out of range, a temp read
+ * before it is written, a non-canonical constant, n_constraints == 0, a limit
+ * exceeded, a nonzero reserved byte, or an output whose formal degree (column
+ * 1, random / const 0, add / sub / neg max, mul sum) exceeds `degree`; a
+ * declared degree above the formal one is allowed, as in the reference.
+ * A program object is host memory only and may be used with any context. */
+typedef struct mlh_cs_program mlh_cs_program;
+#define MLH_CS_MAX_LOG_HEIGHT 32
+mlh_status mlh_cs_program_create(const uint8_t* bytes, uint64_t len, mlh_cs_program** out);
+void mlh_cs_program_destroy(mlh_cs_program* prog);
+uint32_t mlh_cs_program_width(const mlh_cs_program* prog);         /* system.rs:106-108 */
+uint32_t mlh_cs_program_degree(const mlh_cs_program* prog);        /* constraints.rs:31-33 */
+uint32_t mlh_cs_program_n_constraints(const mlh_cs_program* prog); /* constraints.rs:27-29 */
+uint32_t mlh_cs_program_n_randoms(const mlh_cs_program* prog);     /* system.rs:22 */
+/* System::evaluate_composition (evaluation.rs:5-11) on the host: the program
+ * on one row (width values), n_randoms randoms and n_constraints mask
+ * elements; the interpreter mlh_cs_sumcheck_verify uses. */
+mlh_status mlh_cs_program_evaluate(const mlh_cs_program* prog, const uint8_t* host_values,
+                                   const uint8_t* host_randoms, const uint8_t* host_mask,
+                                   uint8_t out[16]);
+/* Launch shape of the first pass over tables of 2^log_height rows: the block
+ * size (from the program's LDS slots) and the number of blocks; a thread
+ * visits ceil(2^(log_height-1) / (threads * blocks)) row pairs. */
+mlh_status mlh_cs_launch_info(const mlh_cs_program* prog, uint32_t log_height, uint32_t* threads,
+                              uint32_t* blocks);
+/* ChallengeSet::new (system.rs:131-146) and the constraint mask (:82-95), as
+ * the reference computes them: `vec![transcript.next_challenge(); n]`
+ * evaluates the call once and clones it, and next_challenge() does not change
+ * the transcript (transcript.rs:35-38), so row_out (log_rows elements),
+ * trace_out (n_randoms) and constraint_out (log2(next_pow2(n_constraints)))
+ * are all filled with the same single challenge and the transcript is left
+ * unchanged.  mask_out[c] = Mask{c, n_vars = log2(next_pow2(n_constraints))}
+ * .evaluate(constraint), n_constraints elements (1 for a single constraint). */
+mlh_status mlh_system_challenges(mlh_transcript* tr, uint32_t log_rows, uint32_t n_randoms,
+                                 uint32_t n_constraints, uint8_t* row_out, uint8_t* trace_out,
+                                 uint8_t* constraint_out, uint8_t* mask_out);
+/* SumcheckTables::partial_sum (sumcheck.rs:204-232) at X = 1..D, D = degree+1
+ * (:159,185): out = D x 16 bytes.  width must equal the program's
+ * (MLH_ERR_INVALID otherwise, as for every call below that takes both);
+ * host_randoms: n_randoms elements (may be NULL when 0), host_mask:
+ * n_constraints elements. */
+mlh_status mlh_cs_partial_sums(mlh_ctx* ctx, const mlh_cs_program* prog, uint32_t width,
+                               const void* dev_matrix, const void* dev_delta, uint32_t log_height,
+                               const uint8_t* host_randoms, const uint8_t* host_mask,
+                               uint8_t* out);
+/* SumcheckTables::fold (sumcheck.rs:234-247) of all columns and delta, in
+ * place: height 2^log_height -> 2^(log_height-1) (the first half). */
+mlh_status mlh_cs_fold(mlh_ctx* ctx, uint32_t width, void* dev_matrix, void* dev_delta,
+                       uint32_t log_height, const uint8_t r[16]);
+/* fold followed by the folded tables' partial sums, one HBM pass
+ * (log_height >= 2). */
+mlh_status mlh_cs_fold_and_sums(mlh_ctx* ctx, const mlh_cs_program* prog, uint32_t width,
+                                void* dev_matrix, void* dev_delta, uint32_t log_height,
+                                const uint8_t* host_randoms, const uint8_t* host_mask,
+                                const uint8_t r[16], uint8_t* out);
+/* System::compute_sumcheck_polynomials (sumcheck.rs:40-53) =
+ * SumcheckTables::compute_sumcheck_polynomials (:147-202): log_height rounds
+ * on the device with one synchronisation at the end; per round the D nonzero
+ * coefficients c1..cD go to polys_out[round][D][16] and the challenge to
+ * rs_out[round][16] (either may be NULL).  Tables are folded in place: on
+ * return row 0 of dev_matrix is Trace::evaluate(rs) and dev_delta[0] is
+ * Delta{row}.evaluate(rs).  The host replays the transcript from the returned
+ * coefficients; if a challenge differs the call returns MLH_ERR_DEVICE and
+ * leaves the transcript unchanged.  log_height == 0 is zero rounds: MLH_OK,
+ * nothing written, transcript untouched.  log_height <=
+ * MLH_CS_MAX_LOG_HEIGHT. */
+mlh_status mlh_cs_sumcheck_prove(mlh_ctx* ctx, const mlh_cs_program* prog, uint32_t width,
+                                 void* dev_matrix, void* dev_delta, uint32_t log_height,
+                                 const uint8_t* host_randoms, const uint8_t* host_mask,
+                                 const uint8_t sum[16], mlh_transcript* tr, uint8_t* polys_out,
+                                 uint8_t* rs_out);
+/* System::verify_with_evaluations (sumcheck.rs:91-124), host only, with
+ * SumcheckPolynomial::to_polynomial's a0 = (sum - sum of coefficients) / 2
+ * (:269-276): host_row_points = the row challenges (log_height elements),
+ * polys = [log_height][D][16], host_output = width elements (Trace::evaluate
+ * at the challenges).  MLH_ERR_VERIFY where the reference asserts (and for a
+ * non-canonical element of polys or host_output); the transcript is then
+ * left as it was.  On MLH_OK it has absorbed every coefficient. */
+mlh_status mlh_cs_sumcheck_verify(const mlh_cs_program* prog, uint32_t log_height,
+                                  const uint8_t* host_row_points, const uint8_t* host_randoms,
+                                  const uint8_t* host_mask, const uint8_t sum[16],
+                                  const uint8_t* polys, const uint8_t* host_output,
+                                  mlh_transcript* tr);
+
 /* ---- multilinear PCS (src/fri/multilinear_pcs.rs) ------------------------ */
 typedef struct mlh_pcs_proof {
   mlh_fri_proof fri;

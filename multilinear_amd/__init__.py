@@ -4,7 +4,8 @@ folding and MLE/sumcheck rounds over the field.rs prime, behind the C ABI in
 include/mlhip.h (libmlhip.so).
 
 The Python modules mirror the reference's public API names (src/ntt,
-src/fri, src/merkle_tree, src/polynomials.rs, sumcheck, multilinear_pcs) so
+src/fri, src/merkle_tree, src/polynomials.rs, sumcheck, multilinear_pcs,
+constraint_system) so
 the parity tests read like the reference's own tests; they are thin ctypes
 wrappers -- all compute runs in the HIP kernels of libmlhip.so.
 """

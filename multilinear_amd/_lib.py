@@ -202,6 +202,20 @@ SIGNATURES = {
     "mlh_sumcheck_fold_and_sums": (_I, [_P, _P, _P, _U32, _P, _P]),
     "mlh_sumcheck_prove": (_I, [_P, _P, _P, _U32, _P, _P, _P, _P]),
     "mlh_sumcheck_prove_eq": (_I, [_P, _P, _P, _U32, _P, _P, _P, _P, _P, _P]),
+    "mlh_cs_program_create": (_I, [_P, _U64, ctypes.POINTER(_P)]),
+    "mlh_cs_program_destroy": (None, [_P]),
+    "mlh_cs_program_width": (_U32, [_P]),
+    "mlh_cs_program_degree": (_U32, [_P]),
+    "mlh_cs_program_n_constraints": (_U32, [_P]),
+    "mlh_cs_program_n_randoms": (_U32, [_P]),
+    "mlh_cs_program_evaluate": (_I, [_P, _P, _P, _P, _P]),
+    "mlh_cs_launch_info": (_I, [_P, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "mlh_system_challenges": (_I, [_P, _U32, _U32, _U32, _P, _P, _P, _P]),
+    "mlh_cs_partial_sums": (_I, [_P, _P, _U32, _P, _P, _U32, _P, _P, _P]),
+    "mlh_cs_fold": (_I, [_P, _U32, _P, _P, _U32, _P]),
+    "mlh_cs_fold_and_sums": (_I, [_P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P]),
+    "mlh_cs_sumcheck_prove": (_I, [_P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P]),
+    "mlh_cs_sumcheck_verify": (_I, [_P, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "mlh_pcs_prove": (_I, [_P, _P, _U32, _P, _P, _P, ctypes.POINTER(PcsProofC)]),
     "mlh_pcs_verify": (_I, [ctypes.POINTER(PcsProofC), _U32, _P, _P, _P]),
     "mlh_bench_ntt": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(ctypes.c_float)]),

@@ -1,0 +1,386 @@
+"""Constraint system (src/constraint_system) on the MI355X: System /
+ChallengeSet / ConstraintSet / Trace and the general sumcheck prover and
+verifier of constraint_system/sumcheck.rs:21-125,147-256.
+
+The reference's ``Expr<F>(fn(&[F], &[F]) -> F)`` (constraints.rs:3-10) becomes
+a constraint program: expressions built here from ``var(j)``, ``rand(k)``,
+integers and ``+ - *`` compile to the straight-line wire format of
+include/mlhip.h, which libmlhip validates, interprets on the device (prover)
+and on the host (verifier).  ``Commitment`` is a placeholder in the reference
+(trace.rs:41-48) and has no counterpart here.
+"""
+import ctypes
+import struct
+
+from .device import M, check, context, fe_bytes, fe_from_bytes, lib, ptr
+from .polynomials import eq_table
+from .transcript import Transcript
+
+OP_ADD, OP_SUB, OP_MUL, OP_NEG = 0, 1, 2, 3
+COL, RAND, CONST, TEMP = 0, 1, 2, 3
+MAX_TEMPS = 32
+
+
+# ---- expressions -------------------------------------------------------------
+
+class Expr:
+    """A node of a constraint expression (leaf: column / random / constant)."""
+
+    __slots__ = ("op", "args")
+
+    def __init__(self, op, *args):
+        self.op = op
+        self.args = args
+
+    @staticmethod
+    def wrap(v):
+        if isinstance(v, Expr):
+            return v
+        if isinstance(v, int):
+            return Expr("const", v % M)  # the integer's residue mod M
+        raise TypeError("constraint expressions take Expr or int operands, not %r" % type(v))
+
+    def __add__(self, o):
+        return Expr("add", self, Expr.wrap(o))
+
+    def __radd__(self, o):
+        return Expr("add", Expr.wrap(o), self)
+
+    def __sub__(self, o):
+        return Expr("sub", self, Expr.wrap(o))
+
+    def __rsub__(self, o):
+        return Expr("sub", Expr.wrap(o), self)
+
+    def __mul__(self, o):
+        return Expr("mul", self, Expr.wrap(o))
+
+    def __rmul__(self, o):
+        return Expr("mul", Expr.wrap(o), self)
+
+    def __neg__(self):
+        return Expr("neg", self)
+
+
+def var(j):
+    """Column j of the row (the closure's ``var[j]``)."""
+    return Expr("var", int(j))
+
+
+def rand(k):
+    """Random challenge k (the closure's second argument)."""
+    return Expr("rand", int(k))
+
+
+def const(v):
+    return Expr.wrap(int(v))
+
+
+# ---- wire format -------------------------------------------------------------
+
+def encode_program(width, n_randoms, consts, n_temps, instrs, outs, degree):
+    """The wire format of include/mlhip.h.  instrs: (op, dst, (kind, index),
+    (kind, index)) -- NEG takes (0, 0) as its second operand; outs: (kind,
+    index) per constraint."""
+    b = struct.pack("<7I", width, n_randoms, len(consts), n_temps, len(instrs), len(outs), degree)
+    b += b"".join(int(c).to_bytes(16, "little") for c in consts)
+    for op, dst, a, bb in instrs:
+        b += bytes([op, dst, a[0], a[1], bb[0], bb[1], 0, 0])
+    for o in outs:
+        b += bytes([o[0], o[1]])
+    return b
+
+
+_OPS = {"add": OP_ADD, "sub": OP_SUB, "mul": OP_MUL}
+
+
+def compile_program(exprs, width, n_randoms, degree):
+    """Expressions -> wire bytes.  Straight-line code in evaluation order; a
+    temp is released when its value has been consumed, the deeper operand of a
+    binary node is evaluated first, and equal constants share a pool entry."""
+    consts, instrs, free, live = [], [], [], [0]
+    need_memo = {}
+
+    def need(e):  # temps needed to evaluate e (Sethi-Ullman)
+        k = id(e)
+        if k not in need_memo:
+            if e.op in ("var", "rand", "const"):
+                need_memo[k] = 0
+            elif e.op == "neg":
+                need_memo[k] = max(1, need(e.args[0]))
+            else:
+                a, b = need(e.args[0]), need(e.args[1])
+                need_memo[k] = max(1, a + 1 if a == b else max(a, b))
+        return need_memo[k]
+
+    def alloc():
+        if free:
+            return free.pop()
+        t = live[0]
+        if t >= MAX_TEMPS:
+            raise ValueError("constraint program needs more than %d temps" % MAX_TEMPS)
+        live[0] += 1
+        return t
+
+    def release(o):
+        if o[0] == TEMP:
+            free.append(o[1])
+
+    def emit(e):
+        if e.op == "var":
+            return (COL, e.args[0])
+        if e.op == "rand":
+            return (RAND, e.args[0])
+        if e.op == "const":
+            if e.args[0] not in consts:
+                consts.append(e.args[0])
+            return (CONST, consts.index(e.args[0]))
+        if e.op == "neg":
+            a = emit(e.args[0])
+            release(a)
+            dst = alloc()
+            instrs.append((OP_NEG, dst, a, (0, 0)))
+            return (TEMP, dst)
+        if need(e.args[1]) > need(e.args[0]):
+            b = emit(e.args[1])
+            a = emit(e.args[0])
+        else:
+            a = emit(e.args[0])
+            b = emit(e.args[1])
+        release(a)
+        release(b)
+        dst = alloc()
+        instrs.append((_OPS[e.op], dst, a, b))
+        return (TEMP, dst)
+
+    outs = [emit(Expr.wrap(e)) for e in exprs]  # (an output's temp is never released)
+    return encode_program(width, n_randoms, consts, live[0], instrs, outs, degree)
+
+
+class Program:
+    """A validated constraint program (mlh_cs_program)."""
+
+    def __init__(self, wire):
+        self.wire = bytes(wire)
+        h = ctypes.c_void_p()
+        buf = (ctypes.c_uint8 * len(self.wire)).from_buffer_copy(self.wire)
+        check(lib().mlh_cs_program_create(buf, len(self.wire), ctypes.byref(h)))
+        self.h = h.value
+        self.width = lib().mlh_cs_program_width(self.h)
+        self.degree = lib().mlh_cs_program_degree(self.h)
+        self.n_constraints = lib().mlh_cs_program_n_constraints(self.h)
+        self.n_randoms = lib().mlh_cs_program_n_randoms(self.h)
+
+    def __del__(self):
+        try:
+            lib().mlh_cs_program_destroy(self.h)
+        except Exception:
+            pass
+
+    def evaluate(self, values, randoms, mask):
+        """ConstraintSet::evaluate (evaluation.rs:21-29) by the host interpreter."""
+        out = (ctypes.c_uint8 * 16)()
+        check(lib().mlh_cs_program_evaluate(self.h, _elems(values), _elems(randoms), _elems(mask),
+                                            out))
+        return fe_from_bytes(out)
+
+    def launch_info(self, log_height):
+        """(threads per block, blocks) of the first pass over 2^log_height rows."""
+        t, b = ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib().mlh_cs_launch_info(self.h, log_height, ctypes.byref(t), ctypes.byref(b)))
+        return t.value, b.value
+
+
+def _elems(vals):
+    vals = list(vals)
+    if not vals:
+        return None
+    return (ctypes.c_uint8 * (16 * len(vals))).from_buffer_copy(
+        b"".join(int(v).to_bytes(16, "little") for v in vals))
+
+
+def _split(raw, n):
+    raw = bytes(raw)
+    return [fe_from_bytes(raw[16 * i:16 * i + 16]) for i in range(n)]
+
+
+# ---- the reference's types ---------------------------------------------------
+
+class ConstraintSet:
+    """constraints.rs:12-34: constraints ``expr = 0`` and their degree."""
+
+    def __init__(self, constraints, degree):
+        self._constraints = [Expr.wrap(e) for e in constraints]
+        self._degree = degree
+
+    def constraints(self):
+        return self._constraints
+
+    def degree(self):
+        return self._degree
+
+
+class WitnessLayout:
+    """system.rs:17-30."""
+
+    def __init__(self, columns, randoms=0, pre_random_columns=0, sum_columns=()):
+        self.columns = columns
+        self.randoms = randoms
+        self.pre_random_columns = pre_random_columns
+        self.sum_columns = tuple(sum_columns)
+
+
+class Trace:
+    """trace.rs:5-39: a row-major height x width matrix on the device
+    ((height * width, 4) int32 limbs)."""
+
+    def __init__(self, dev_matrix, width):
+        n = dev_matrix.shape[0]
+        assert width >= 1 and n % width == 0
+        self._matrix = dev_matrix
+        self._width = width
+        self._height = n // width
+        assert self._height & (self._height - 1) == 0 and self._height > 0
+
+    def matrix(self):
+        return self._matrix
+
+    def width(self):
+        return self._width
+
+    def height(self):
+        return self._height
+
+    def evaluate(self, points, device=0):
+        """evaluation.rs:31-48 (mlh_trace_evaluate)."""
+        ctx = context(device)
+        out = (ctypes.c_uint8 * (16 * self._width))()
+        check(lib().mlh_trace_evaluate(ctx, ptr(self._matrix), self._height.bit_length() - 1,
+                                       self._width, _elems(points), out), ctx)
+        return _split(out, self._width)
+
+
+class ChallengeSet:
+    """system.rs:32-36,131-159, with the constraint mask of System::new
+    (:90-95) from the same call (mlh_system_challenges)."""
+
+    def __init__(self, transcript, num_randoms, num_constraints, log_num_rows):
+        log_nc = max(num_constraints - 1, 0).bit_length()
+        row = (ctypes.c_uint8 * (16 * max(log_num_rows, 1)))()
+        trace = (ctypes.c_uint8 * (16 * max(num_randoms, 1)))()
+        cons = (ctypes.c_uint8 * (16 * max(log_nc, 1)))()
+        mask = (ctypes.c_uint8 * (16 * max(num_constraints, 1)))()
+        check(lib().mlh_system_challenges(transcript.h, log_num_rows, num_randoms, num_constraints,
+                                          row, trace, cons, mask))
+        self._row = _split(row, log_num_rows)
+        self._trace = _split(trace, num_randoms)
+        self._constraint = _split(cons, log_nc)
+        self.mask = _split(mask, num_constraints)
+
+    def row(self):
+        return self._row
+
+    def trace(self):
+        return self._trace
+
+    def constraint(self):
+        return self._constraint
+
+
+class SumcheckTables:
+    """sumcheck.rs:10-15: the matrix, its width and height, delta."""
+
+    def __init__(self, matrix, width, height, delta):
+        self.matrix = matrix
+        self.width = width
+        self.height = height
+        self.delta = delta
+
+
+class System:
+    """system.rs:8-129 with the sumcheck methods of sumcheck.rs:21-125."""
+
+    def __init__(self, transcript, constraints, layout, log_num_rows, trace, device=0):
+        self._constraints = constraints
+        self._layout = layout
+        self._trace = trace
+        self._device = device
+        n = len(constraints.constraints())
+        self._challenges = ChallengeSet(transcript, layout.randoms, n, log_num_rows)
+        self._constraint_mask = self._challenges.mask
+        self.program = Program(compile_program(constraints.constraints(), layout.columns,
+                                               layout.randoms, constraints.degree()))
+
+    @staticmethod
+    def prover(transcript, constraints, layout, trace, device=0):  # system.rs:56-72
+        return System(transcript, constraints, layout, trace.height().bit_length() - 1, trace,
+                      device)
+
+    @staticmethod
+    def verifier(transcript, constraints, layout, log_num_rows, device=0):  # system.rs:39-54
+        return System(transcript, constraints, layout, log_num_rows, None, device)
+
+    def num_columns(self):
+        return self._layout.columns
+
+    def constraints(self):
+        return self._constraints
+
+    def constraint_mask(self):
+        return self._constraint_mask
+
+    def challenges(self):
+        return self._challenges
+
+    def trace(self):
+        return self._trace
+
+    def evaluate_composition(self, outputs):  # evaluation.rs:5-11
+        assert len(outputs) == self.num_columns()
+        return self.program.evaluate(outputs, self._challenges.trace(), self._constraint_mask)
+
+    def build_tables(self):
+        """sumcheck.rs:22-38: a clone of the trace's matrix and delta = the eq
+        table of the row challenges (mlh_eq_table)."""
+        t = self._trace
+        delta = eq_table(self._challenges.row(), self._device)
+        return SumcheckTables(t.matrix().clone(), t.width(), t.height(), delta)
+
+    def compute_sumcheck_polynomials(self, transcript: Transcript, tables, total_sum):
+        """sumcheck.rs:40-53 -> ([nonzero coefficients c1..cD] per round, [r]);
+        the tables are folded in place down to height 1."""
+        ctx = context(self._device)
+        n = tables.height.bit_length() - 1
+        D = self._constraints.degree() + 1
+        polys = (ctypes.c_uint8 * (16 * D * max(n, 1)))()
+        rs = (ctypes.c_uint8 * (16 * max(n, 1)))()
+        check(lib().mlh_cs_sumcheck_prove(ctx, self.program.h, tables.width, ptr(tables.matrix),
+                                          ptr(tables.delta), n, _elems(self._challenges.trace()),
+                                          _elems(self._constraint_mask), fe_bytes(total_sum),
+                                          transcript.h, polys, rs), ctx)
+        tables.height = 1
+        flat = _split(polys, D * n)
+        return [flat[D * k:D * k + D] for k in range(n)], _split(rs, n)
+
+    def verify_with_evaluations(self, transcript: Transcript, pols, total_sum, output):
+        """sumcheck.rs:91-124 on the host; raises MlhError (MLH_ERR_VERIFY)
+        where the reference asserts."""
+        n = len(pols)
+        flat = [c for p in pols for c in p]
+        check(lib().mlh_cs_sumcheck_verify(self.program.h, n, _elems(self._challenges.row()),
+                                           _elems(self._challenges.trace()),
+                                           _elems(self._constraint_mask), fe_bytes(total_sum),
+                                           _elems(flat), _elems(output), transcript.h))
+
+    def verify_sumcheck_debug(self, transcript: Transcript, pols, total_sum):
+        """sumcheck.rs:55-89: as verify_with_evaluations with the output taken
+        from the prover's own trace at the challenges, which a clone of the
+        transcript replays first."""
+        t = transcript.clone()
+        rs = []
+        for p in pols:
+            for c in p:
+                t.absorb(int(c).to_bytes(16, "little"))
+            rs.append(t.next_challenge())
+        output = self._trace.evaluate(rs, self._device)
+        self.verify_with_evaluations(transcript, pols, total_sum, output)

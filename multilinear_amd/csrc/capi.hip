@@ -30,6 +30,8 @@
 #include "host_sha256.hpp"
 #include "host_transcript.hpp"
 #include "context.hpp"
+#include "cs_program.hpp"
+#include "cs_sumcheck.hpp"
 #include "fused_ntt.hpp"
 #include "merkle.hpp"
 #include "ntt.hpp"
@@ -2672,6 +2674,179 @@ mlh_status mlh_device_sumcheck_round(mlh_ctx* ctx, const void* dev_sum_pairs, ui
                                      reinterpret_cast<DevSha*>(dev_state),
                                      reinterpret_cast<fe*>(dev_poly_out),
                                      reinterpret_cast<fe*>(dev_r_out), ctx->stream));
+  return MLH_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// constraint-system sumcheck (constraint_system/sumcheck.rs:40-53,147-247):
+// width-W tables, the composition a constraint program (cs_program.hpp)
+// ---------------------------------------------------------------------------
+// One call's device image of a program: the uniform pool (this call's randoms
+// and mask beside the program's constants), the interpolation matrix and the
+// instruction words, in one pooled buffer filled by one copy.
+struct CsCall {
+  PoolBuf buf;
+  std::vector<uint8_t> img;  // (kept until the call's sync: the copy's source)
+  CsDev dev{};
+  const fe* vinv = nullptr;
+  uint32_t threads = 0;
+  explicit CsCall(mlh_ctx* c) : buf(c) {}
+  mlh_status init(mlh_ctx* ctx, const mlh_cs_program* prog, const uint8_t* host_randoms,
+                  const uint8_t* host_mask) {
+    const CsProgram& p = prog->p;
+    std::vector<u128> rnd(p.n_randoms), mask(p.n_constraints);
+    for (uint32_t i = 0; i < p.n_randoms; ++i)
+      if ((rnd[i] = h_load(host_randoms + 16ull * i)) >= kModulus)
+        return fail(ctx, MLH_ERR_INVALID, "non-canonical random");
+    for (uint32_t i = 0; i < p.n_constraints; ++i)
+      if ((mask[i] = h_load(host_mask + 16ull * i)) >= kModulus)
+        return fail(ctx, MLH_ERR_INVALID, "non-canonical mask");
+    const CsImageLayout l = cs_image_layout(p);
+    img = cs_build_image(p, rnd.data(), mask.data());
+    MLH_TRY(buf.alloc(l.bytes));
+    HIP_TRY(ctx, hipMemcpyAsync(buf.p, img.data(), l.bytes, hipMemcpyHostToDevice, ctx->stream));
+    const uint8_t* b = buf.as<uint8_t>();
+    dev.uni = reinterpret_cast<const fe*>(b);
+    dev.code = reinterpret_cast<const uint32_t*>(b + l.code_off);
+    dev.outs = reinterpret_cast<const uint32_t*>(b + l.outs_off);
+    dev.width = p.width;
+    dev.n_temps = p.n_temps;
+    dev.n_instr = p.n_instr;
+    dev.n_constraints = p.n_constraints;
+    dev.D = p.points();
+    vinv = dev.uni + l.vinv_off;
+    threads = cs_threads(cs_slots(p));
+    return MLH_OK;
+  }
+};
+
+static bool cs_args_ok(const mlh_cs_program* prog, uint32_t width, const void* m, const void* d,
+                       const uint8_t* randoms, const uint8_t* mask) {
+  return prog && m && d && mask && width == prog->p.width && (!prog->p.n_randoms || randoms);
+}
+
+static mlh_status cs_read_sums(mlh_ctx* ctx, const CsCall& cc, uint32_t nb, uint8_t* out) {
+  HIP_TRY(ctx, launch_cs_reduce(ctx->partials, nb, cc.dev.D, ctx->small, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, ctx->small, 16ull * cc.dev.D, hipMemcpyDeviceToHost,
+                              ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(out, ctx->pinned, 16ull * cc.dev.D);
+  return MLH_OK;
+}
+
+extern "C" {
+
+mlh_status mlh_cs_partial_sums(mlh_ctx* ctx, const mlh_cs_program* prog, uint32_t width,
+                               const void* dev_matrix, const void* dev_delta, uint32_t log_height,
+                               const uint8_t* host_randoms, const uint8_t* host_mask,
+                               uint8_t* out) {
+  if (!ctx || !out || !cs_args_ok(prog, width, dev_matrix, dev_delta, host_randoms, host_mask) ||
+      log_height < 1 || log_height > kCsMaxLogHeight)
+    return fail(ctx, MLH_ERR_INVALID, "bad argument");
+  CsCall cc(ctx);
+  MLH_TRY(cc.init(ctx, prog, host_randoms, host_mask));
+  uint32_t nb = 0;
+  HIP_TRY(ctx, launch_cs_sums(cc.dev, cc.threads, reinterpret_cast<const fe*>(dev_matrix),
+                              reinterpret_cast<const fe*>(dev_delta), 1ull << (log_height - 1),
+                              ctx->partials, ctx->stream, &nb));
+  return cs_read_sums(ctx, cc, nb, out);
+}
+
+mlh_status mlh_cs_fold(mlh_ctx* ctx, uint32_t width, void* dev_matrix, void* dev_delta,
+                       uint32_t log_height, const uint8_t r[16]) {
+  if (!ctx || !dev_matrix || !dev_delta || !r || width < 1 || width > kCsMaxWidth ||
+      log_height < 1 || log_height > kCsMaxLogHeight || h_load(r) >= kModulus)
+    return fail(ctx, MLH_ERR_INVALID, "bad argument");
+  HIP_TRY(ctx, launch_cs_fold(width, reinterpret_cast<fe*>(dev_matrix),
+                              reinterpret_cast<fe*>(dev_delta), 1ull << log_height,
+                              to_fe(h_load(r)), nullptr, ctx->stream));
+  return MLH_OK;
+}
+
+mlh_status mlh_cs_fold_and_sums(mlh_ctx* ctx, const mlh_cs_program* prog, uint32_t width,
+                                void* dev_matrix, void* dev_delta, uint32_t log_height,
+                                const uint8_t* host_randoms, const uint8_t* host_mask,
+                                const uint8_t r[16], uint8_t* out) {
+  if (!ctx || !out || !r || !cs_args_ok(prog, width, dev_matrix, dev_delta, host_randoms, host_mask) ||
+      log_height < 2 || log_height > kCsMaxLogHeight || h_load(r) >= kModulus)
+    return fail(ctx, MLH_ERR_INVALID, "bad argument");
+  CsCall cc(ctx);
+  MLH_TRY(cc.init(ctx, prog, host_randoms, host_mask));
+  uint32_t nb = 0;
+  HIP_TRY(ctx, launch_cs_fold_sums(cc.dev, cc.threads, reinterpret_cast<fe*>(dev_matrix),
+                                   reinterpret_cast<fe*>(dev_delta), 1ull << log_height,
+                                   to_fe(h_load(r)), nullptr, ctx->partials, ctx->stream, &nb));
+  return cs_read_sums(ctx, cc, nb, out);
+}
+
+mlh_status mlh_cs_sumcheck_prove(mlh_ctx* ctx, const mlh_cs_program* prog, uint32_t width,
+                                 void* dev_matrix, void* dev_delta, uint32_t log_height,
+                                 const uint8_t* host_randoms, const uint8_t* host_mask,
+                                 const uint8_t sum[16], mlh_transcript* tr, uint8_t* polys_out,
+                                 uint8_t* rs_out) {
+  if (!ctx || !sum || !tr || !cs_args_ok(prog, width, dev_matrix, dev_delta, host_randoms, host_mask) ||
+      log_height > kCsMaxLogHeight || h_load(sum) >= kModulus)
+    return fail(ctx, MLH_ERR_INVALID, "bad argument");
+  const uint32_t L = log_height;
+  if (L == 0) return MLH_OK;  // zero rounds (sumcheck.rs:160-161)
+  CsCall cc(ctx);
+  MLH_TRY(cc.init(ctx, prog, host_randoms, host_mask));
+  const uint32_t D = cc.dev.D;
+  // [DevSha | claim | polys 16 D x L | rs 16 x L]; one sync, at the end
+  const uint64_t out_bytes = 16ull * (D + 1) * L;
+  PoolBuf sc(ctx);
+  MLH_TRY(sc.alloc(144 + out_bytes));
+  uint8_t* sb = sc.as<uint8_t>();
+  DevSha* dt = reinterpret_cast<DevSha*>(sb);
+  fe* prev = reinterpret_cast<fe*>(sb + 128);
+  fe* polys = reinterpret_cast<fe*>(sb + 144);
+  fe* rs = polys + (uint64_t)D * L;
+  static_assert(sizeof(DevSha) <= 128, "DevSha slot");
+  memcpy(ctx->pinned, &tr->sha, sizeof(DevSha));
+  memcpy(ctx->pinned + 128, sum, 16);
+  HIP_TRY(ctx, hipMemcpyAsync(sb, ctx->pinned, 144, hipMemcpyHostToDevice, ctx->stream));
+  fe* m = reinterpret_cast<fe*>(dev_matrix);
+  fe* d = reinterpret_cast<fe*>(dev_delta);
+  uint32_t nb = 0;
+  {
+    ProfScope ps(ctx, "cs_sums");
+    HIP_TRY(ctx, launch_cs_sums(cc.dev, cc.threads, m, d, 1ull << (L - 1), ctx->partials,
+                                ctx->stream, &nb));
+    ps.end();
+  }
+  for (uint32_t k = 0; k < L; ++k) {
+    {
+      ProfScope ps(ctx, "cs_round");
+      HIP_TRY(ctx, launch_cs_round(ctx->partials, nb, D, cc.vinv, prev, dt, polys + (uint64_t)D * k,
+                                   rs + k, ctx->stream));
+      ps.end();
+    }
+    const uint64_t S = 1ull << (L - k);
+    if (S >= 4) {  // fold with r_k + round k+1's sums, one pass
+      ProfScope ps(ctx, "cs_fold_sums");
+      HIP_TRY(ctx, launch_cs_fold_sums(cc.dev, cc.threads, m, d, S, fe{}, rs + k, ctx->partials,
+                                       ctx->stream, &nb));
+      ps.end();
+    } else {
+      ProfScope ps(ctx, "cs_fold");
+      HIP_TRY(ctx, launch_cs_fold(width, m, d, S, fe{}, rs + k, ctx->stream));
+      ps.end();
+    }
+  }
+  static_assert(16ull * (kCsMaxDegree + 2) * kCsMaxLogHeight <= kPinStage, "prove staging");
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, polys, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<uint8_t> host(ctx->pinned, ctx->pinned + out_bytes);
+  ReplayCheck rc(ctx, tr);
+  for (uint32_t k = 0; k < L; ++k) {  // host transcript replay (sumcheck.rs:194-198)
+    for (uint32_t j = 0; j < D; ++j) rc.absorb(host.data() + 16ull * (k * D + j), 16);
+    rc.expect(host.data() + 16ull * D * L + 16ull * k);
+  }
+  MLH_TRY(rc.status());
+  if (polys_out) memcpy(polys_out, host.data(), 16ull * D * L);
+  if (rs_out) memcpy(rs_out, host.data() + 16ull * D * L, 16ull * L);
   return MLH_OK;
 }
 

@@ -1,0 +1,247 @@
+// Constraint programs: the straight-line form of the reference's
+// Expr<F>(fn(&[F], &[F]) -> F) (constraint_system/constraints.rs:3-10) and
+// ConstraintSet::evaluate (evaluation.rs:21-29).  One decoder (cs_decode) for
+// the wire format of include/mlhip.h, one decoded form (CsProgram) and its
+// device image (CsImage: the words cs_sumcheck.hip's interpreter reads), and
+// the host interpreter (cs_host_eval) the verifier uses.  Plain C++: no HIP
+// dependency, so verify.cpp keeps building for the host sanitizers.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "host_field.hpp"
+
+namespace mlh {
+
+// wire / decoded opcodes and operand kinds (include/mlhip.h)
+enum : uint8_t { kCsAdd = 0, kCsSub = 1, kCsMul = 2, kCsNeg = 3 };
+enum : uint8_t { kCsCol = 0, kCsRand = 1, kCsConst = 2, kCsTemp = 3 };
+
+constexpr uint32_t kCsMaxWidth = 32, kCsMaxTemps = 32, kCsMaxConsts = 64, kCsMaxRandoms = 64;
+constexpr uint32_t kCsMaxConstraints = 256, kCsMaxInstr = 4096, kCsMaxDegree = 7;
+constexpr uint32_t kCsHeaderBytes = 28, kCsInstrBytes = 8, kCsOperandBytes = 2;
+constexpr uint32_t kCsMaxLogHeight = 32;
+
+// Device operand: bit 15 set = a wave-uniform value, index into the uniform
+// pool [randoms | consts | mask]; clear = a per-lane LDS slot, columns first
+// (slot j = column j's value at the current X), then temps (width + t).
+constexpr uint32_t kCsUniform = 0x8000u;
+
+struct CsOperand {
+  uint8_t kind, index;
+};
+struct CsInstr {
+  uint8_t op, dst;
+  CsOperand a, b;
+};
+
+struct CsProgram {
+  uint32_t width = 0, n_randoms = 0, n_consts = 0, n_temps = 0, n_instr = 0, n_constraints = 0;
+  uint32_t degree = 0;
+  std::vector<u128> consts;
+  std::vector<CsInstr> instr;
+  std::vector<CsOperand> outs;
+  // inverse Vandermonde matrix of the points 0..degree+1 (row k = coefficient
+  // k's weights on the evaluations): the exact interpolation of
+  // PolynomialEvals::interpolate (polynomials.rs:51-87) as one product
+  std::vector<u128> vinv;
+  uint32_t points() const { return degree + 1; }  // D: X = 1..D (sumcheck.rs:159,185)
+};
+
+static inline uint32_t cs_rd32(const uint8_t* p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+// (n+1) x (n+1) inverse Vandermonde of the points 0..n: column j holds the
+// coefficients of the Lagrange basis polynomial L_j.
+static inline std::vector<u128> cs_inverse_vandermonde(uint32_t n) {
+  const uint32_t N = n + 1;
+  std::vector<u128> out((size_t)N * N, 0);
+  for (uint32_t j = 0; j < N; ++j) {
+    std::vector<u128> lj(1, 1);
+    u128 denom = 1;
+    for (uint32_t m = 0; m < N; ++m) {
+      if (m == j) continue;
+      std::vector<u128> nx(lj.size() + 1, 0);  // lj *= (x - m)
+      for (size_t i = 0; i < lj.size(); ++i) {
+        nx[i] = h_sub(nx[i], h_mul(lj[i], (u128)m));
+        nx[i + 1] = h_add(nx[i + 1], lj[i]);
+      }
+      lj.swap(nx);
+      denom = h_mul(denom, h_sub((u128)j, (u128)m));
+    }
+    const u128 s = h_inv(denom);
+    for (uint32_t k = 0; k < N; ++k) out[(size_t)k * N + j] = h_mul(lj[k], s);
+  }
+  return out;
+}
+
+// Decode and validate a wire-format program; false = MLH_ERR_INVALID.
+static inline bool cs_decode(const uint8_t* b, uint64_t len, CsProgram& p) {
+  if (!b || len < kCsHeaderBytes) return false;
+  p.width = cs_rd32(b);
+  p.n_randoms = cs_rd32(b + 4);
+  p.n_consts = cs_rd32(b + 8);
+  p.n_temps = cs_rd32(b + 12);
+  p.n_instr = cs_rd32(b + 16);
+  p.n_constraints = cs_rd32(b + 20);
+  p.degree = cs_rd32(b + 24);
+  if (p.width < 1 || p.width > kCsMaxWidth || p.n_randoms > kCsMaxRandoms ||
+      p.n_consts > kCsMaxConsts || p.n_temps > kCsMaxTemps || p.n_instr > kCsMaxInstr ||
+      p.n_constraints < 1 || p.n_constraints > kCsMaxConstraints || p.degree < 1 ||
+      p.degree > kCsMaxDegree)
+    return false;
+  const uint64_t want = (uint64_t)kCsHeaderBytes + 16ull * p.n_consts +
+                        (uint64_t)kCsInstrBytes * p.n_instr +
+                        (uint64_t)kCsOperandBytes * p.n_constraints;
+  if (len != want) return false;  // truncated, or trailing bytes
+  const uint8_t* q = b + kCsHeaderBytes;
+  p.consts.resize(p.n_consts);
+  for (uint32_t i = 0; i < p.n_consts; ++i, q += 16) {
+    p.consts[i] = h_load(q);
+    if (p.consts[i] >= kModulus) return false;
+  }
+  // formal degree: column 1, random / const 0, add / sub / neg max, mul sum
+  uint32_t tdeg[kCsMaxTemps];
+  bool twritten[kCsMaxTemps] = {};
+  bool ok = true;
+  auto opdeg = [&](const CsOperand& o) -> uint32_t {
+    switch (o.kind) {
+      case kCsCol: ok = ok && o.index < p.width; return 1;
+      case kCsRand: ok = ok && o.index < p.n_randoms; return 0;
+      case kCsConst: ok = ok && o.index < p.n_consts; return 0;
+      case kCsTemp:
+        ok = ok && o.index < p.n_temps && twritten[o.index];  // read before written
+        return ok ? tdeg[o.index] : 0;
+      default: ok = false; return 0;
+    }
+  };
+  p.instr.resize(p.n_instr);
+  for (uint32_t i = 0; i < p.n_instr; ++i, q += kCsInstrBytes) {
+    CsInstr in{q[0], q[1], {q[2], q[3]}, {q[4], q[5]}};
+    if (in.op > kCsNeg || in.dst >= p.n_temps || q[6] || q[7]) return false;
+    const uint32_t da = opdeg(in.a);
+    uint32_t d = da;
+    if (in.op == kCsNeg) {
+      if (in.b.kind || in.b.index) return false;  // NEG: b is (0, 0)
+    } else {
+      const uint32_t db = opdeg(in.b);
+      d = in.op == kCsMul ? da + db : (da > db ? da : db);
+    }
+    if (!ok) return false;
+    tdeg[in.dst] = d > 0xFFFFu ? 0xFFFFu : d;  // (saturating: any such value exceeds degree)
+    twritten[in.dst] = true;
+    p.instr[i] = in;
+  }
+  p.outs.resize(p.n_constraints);
+  for (uint32_t c = 0; c < p.n_constraints; ++c, q += kCsOperandBytes) {
+    p.outs[c] = CsOperand{q[0], q[1]};
+    const uint32_t d = opdeg(p.outs[c]);
+    if (!ok || d > p.degree) return false;
+  }
+  p.vinv = cs_inverse_vandermonde(p.degree + 1);
+  return true;
+}
+
+// ConstraintSet::evaluate (evaluation.rs:21-29): sum_c mask[c] * out_c(values, randoms).
+static inline u128 cs_host_eval(const CsProgram& p, const u128* values, const u128* randoms,
+                                const u128* mask) {
+  u128 temps[kCsMaxTemps] = {};
+  auto get = [&](const CsOperand& o) -> u128 {
+    switch (o.kind) {
+      case kCsCol: return values[o.index];
+      case kCsRand: return randoms[o.index];
+      case kCsConst: return p.consts[o.index];
+      default: return temps[o.index];
+    }
+  };
+  for (const CsInstr& in : p.instr) {
+    const u128 a = get(in.a);
+    u128 r;
+    switch (in.op) {
+      case kCsAdd: r = h_add(a, get(in.b)); break;
+      case kCsSub: r = h_sub(a, get(in.b)); break;
+      case kCsMul: r = h_mul(a, get(in.b)); break;
+      default: r = h_sub(0, a); break;
+    }
+    temps[in.dst] = r;
+  }
+  u128 acc = 0;
+  for (uint32_t c = 0; c < p.n_constraints; ++c) acc = h_add(acc, h_mul(mask[c], get(p.outs[c])));
+  return acc;
+}
+
+// ---- device image ------------------------------------------------------------
+// 16-byte elements first: uniform pool [randoms | consts | mask], then the
+// inverse Vandermonde matrix ((D+1)^2); then 32-bit words: per instruction
+// (op | dst slot << 8, a | b << 16), per constraint (out | mask index << 16).
+struct CsImageLayout {
+  uint32_t n_uni, vinv_off /* elements */, code_off /* bytes */, outs_off /* bytes */, bytes;
+};
+static inline CsImageLayout cs_image_layout(const CsProgram& p) {
+  CsImageLayout l;
+  l.n_uni = p.n_randoms + p.n_consts + p.n_constraints;
+  l.vinv_off = l.n_uni;
+  const uint32_t N = p.degree + 2;
+  l.code_off = 16 * (l.n_uni + N * N);
+  l.outs_off = l.code_off + 8 * p.n_instr;
+  l.bytes = (l.outs_off + 4 * p.n_constraints + 15) & ~15u;
+  return l;
+}
+static inline uint32_t cs_dev_operand(const CsProgram& p, const CsOperand& o) {
+  switch (o.kind) {
+    case kCsCol: return o.index;
+    case kCsTemp: return p.width + o.index;
+    case kCsRand: return kCsUniform | o.index;
+    default: return kCsUniform | (p.n_randoms + o.index);
+  }
+}
+static inline std::vector<uint8_t> cs_build_image(const CsProgram& p, const u128* randoms,
+                                                  const u128* mask) {
+  const CsImageLayout l = cs_image_layout(p);
+  std::vector<uint8_t> img(l.bytes, 0);
+  uint8_t* q = img.data();
+  for (uint32_t i = 0; i < p.n_randoms; ++i, q += 16) h_store(q, randoms[i]);
+  for (uint32_t i = 0; i < p.n_consts; ++i, q += 16) h_store(q, p.consts[i]);
+  for (uint32_t i = 0; i < p.n_constraints; ++i, q += 16) h_store(q, mask[i]);
+  for (u128 v : p.vinv) {
+    h_store(q, v);
+    q += 16;
+  }
+  uint32_t* w = reinterpret_cast<uint32_t*>(img.data() + l.code_off);
+  for (const CsInstr& in : p.instr) {
+    *w++ = (uint32_t)in.op | ((p.width + in.dst) << 8);
+    *w++ = cs_dev_operand(p, in.a) | ((in.op == kCsNeg ? 0u : cs_dev_operand(p, in.b)) << 16);
+  }
+  for (uint32_t c = 0; c < p.n_constraints; ++c)
+    *w++ = cs_dev_operand(p, p.outs[c]) | ((p.n_randoms + p.n_consts + c) << 16);
+  return img;
+}
+
+// Launch shape of the streaming kernels: LDS slots per lane = width (values at
+// X) + width (their step hi - lo) + temps + D (running sums); the block is the
+// largest of 256 / 128 / 64 threads whose slots fit kCsLdsBytes; a block takes
+// at least kCsRowsPerThread row pairs per thread before the grid grows, up to
+// kCsMaxBlocks blocks (the partials buffer holds D * kCsMaxBlocks sums).
+constexpr uint32_t kCsLdsBytes = 152 * 1024;  // of the CU's 160 KiB (the rest: reduction scratch)
+constexpr uint32_t kCsRowsPerThread = 4, kCsMaxBlocks = 512;
+static inline uint32_t cs_slots(const CsProgram& p) { return 2 * p.width + p.n_temps + p.points(); }
+static inline uint32_t cs_threads(uint32_t slots) {
+  uint32_t t = 256;
+  while (t > 64 && slots * 16 * t > kCsLdsBytes) t >>= 1;
+  return t;
+}
+static inline uint32_t cs_blocks(uint64_t pairs, uint32_t threads) {
+  const uint64_t per = (uint64_t)threads * kCsRowsPerThread;
+  uint64_t b = (pairs + per - 1) / per;
+  if (b > kCsMaxBlocks) b = kCsMaxBlocks;
+  return b ? (uint32_t)b : 1;
+}
+
+}  // namespace mlh
+
+struct mlh_cs_program {
+  mlh::CsProgram p;
+};

@@ -8,9 +8,11 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <memory>
 #include <vector>
 
 #include "../../include/mlhip.h"
+#include "cs_program.hpp"
 #include "host_field.hpp"
 #include "host_sha256.hpp"
 #include "host_transcript.hpp"
@@ -366,6 +368,147 @@ mlh_status mlh_batched_pcs_verify(const mlh_batched_pcs_proof* pf, uint32_t n_va
   }
   if (h_mul(delta, h_load(fp->last_elem)) != val) return MLH_ERR_VERIFY;
   return batched_verify_queries(fp, tr, rs, fr);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// constraint system: programs, challenges, the sumcheck verifier
+// (constraint_system/{constraints,system,evaluation,sumcheck}.rs)
+// ---------------------------------------------------------------------------
+static bool load_canonical(const uint8_t* src, uint32_t n, std::vector<u128>& out) {
+  out.resize(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    out[i] = h_load(src + 16ull * i);
+    if (out[i] >= kModulus) return false;
+  }
+  return true;
+}
+
+// Mask::evaluate (evaluation.rs:56-73)
+static u128 mask_evaluate(uint64_t index, uint32_t n_vars, const u128* points) {
+  u128 acc = 1;
+  for (uint32_t i = 0; i < n_vars; ++i) {
+    const u128 p = points[n_vars - 1 - i];
+    acc = h_mul(acc, ((index >> i) & 1) ? p : h_sub(1, p));
+  }
+  return acc;
+}
+
+// Polynomial::evaluate (polynomials.rs:9-14)
+static u128 horner(const std::vector<u128>& c, u128 x) {
+  u128 acc = 0;
+  for (size_t i = c.size(); i-- > 0;) acc = h_add(h_mul(acc, x), c[i]);
+  return acc;
+}
+
+extern "C" {
+
+mlh_status mlh_cs_program_create(const uint8_t* bytes, uint64_t len, mlh_cs_program** out) {
+  if (!bytes || !out) return MLH_ERR_INVALID;
+  std::unique_ptr<mlh_cs_program> p(new mlh_cs_program());
+  if (!cs_decode(bytes, len, p->p)) return MLH_ERR_INVALID;
+  *out = p.release();
+  return MLH_OK;
+}
+void mlh_cs_program_destroy(mlh_cs_program* prog) { delete prog; }
+uint32_t mlh_cs_program_width(const mlh_cs_program* prog) { return prog ? prog->p.width : 0; }
+uint32_t mlh_cs_program_degree(const mlh_cs_program* prog) { return prog ? prog->p.degree : 0; }
+uint32_t mlh_cs_program_n_constraints(const mlh_cs_program* prog) {
+  return prog ? prog->p.n_constraints : 0;
+}
+uint32_t mlh_cs_program_n_randoms(const mlh_cs_program* prog) {
+  return prog ? prog->p.n_randoms : 0;
+}
+
+mlh_status mlh_cs_program_evaluate(const mlh_cs_program* prog, const uint8_t* host_values,
+                                   const uint8_t* host_randoms, const uint8_t* host_mask,
+                                   uint8_t out[16]) {
+  if (!prog || !host_values || !host_mask || !out || (prog->p.n_randoms && !host_randoms))
+    return MLH_ERR_INVALID;
+  std::vector<u128> v, r, m;
+  if (!load_canonical(host_values, prog->p.width, v) ||
+      !load_canonical(host_randoms, prog->p.n_randoms, r) ||
+      !load_canonical(host_mask, prog->p.n_constraints, m))
+    return MLH_ERR_INVALID;
+  h_store(out, cs_host_eval(prog->p, v.data(), r.data(), m.data()));
+  return MLH_OK;
+}
+
+mlh_status mlh_cs_launch_info(const mlh_cs_program* prog, uint32_t log_height, uint32_t* threads,
+                              uint32_t* blocks) {
+  if (!prog || !threads || !blocks || log_height < 1 || log_height > kCsMaxLogHeight)
+    return MLH_ERR_INVALID;
+  *threads = cs_threads(cs_slots(prog->p));
+  *blocks = cs_blocks(1ull << (log_height - 1), *threads);
+  return MLH_OK;
+}
+
+mlh_status mlh_system_challenges(mlh_transcript* tr, uint32_t log_rows, uint32_t n_randoms,
+                                 uint32_t n_constraints, uint8_t* row_out, uint8_t* trace_out,
+                                 uint8_t* constraint_out, uint8_t* mask_out) {
+  uint32_t log_nc = 0;  // next_power_of_two().trailing_zeros() (system.rs:83-87)
+  while ((1ull << log_nc) < n_constraints) ++log_nc;
+  if (!tr || log_rows > 64 || (log_rows && !row_out) || (n_randoms && !trace_out) ||
+      (log_nc && !constraint_out) || (n_constraints && !mask_out))
+    return MLH_ERR_INVALID;
+  // vec![transcript.next_challenge(); n] evaluates the call once and clones it,
+  // and next_challenge() leaves the state as it was (transcript.rs:35-38): one
+  // value fills all three vectors (system.rs:138-140)
+  uint8_t c[16];
+  mlh_transcript_next_challenge(tr, c);
+  for (uint32_t i = 0; i < log_rows; ++i) memcpy(row_out + 16ull * i, c, 16);
+  for (uint32_t i = 0; i < n_randoms; ++i) memcpy(trace_out + 16ull * i, c, 16);
+  for (uint32_t i = 0; i < log_nc; ++i) memcpy(constraint_out + 16ull * i, c, 16);
+  const std::vector<u128> pts(log_nc, h_load(c));
+  for (uint32_t k = 0; k < n_constraints; ++k)  // system.rs:93-95
+    h_store(mask_out + 16ull * k, mask_evaluate(k, log_nc, pts.data()));
+  return MLH_OK;
+}
+
+mlh_status mlh_cs_sumcheck_verify(const mlh_cs_program* prog, uint32_t log_height,
+                                  const uint8_t* host_row_points, const uint8_t* host_randoms,
+                                  const uint8_t* host_mask, const uint8_t sum[16],
+                                  const uint8_t* polys, const uint8_t* host_output,
+                                  mlh_transcript* tr) {
+  if (!prog || !host_row_points || !host_mask || !sum || !polys || !host_output || !tr ||
+      log_height < 1 || log_height > kCsMaxLogHeight || (prog->p.n_randoms && !host_randoms))
+    return MLH_ERR_INVALID;
+  const CsProgram& P = prog->p;
+  const uint32_t L = log_height, D = P.points();
+  std::vector<u128> row, rnd, mask, output, co;
+  if (!load_canonical(host_row_points, L, row) || !load_canonical(host_randoms, P.n_randoms, rnd) ||
+      !load_canonical(host_mask, P.n_constraints, mask) || h_load(sum) >= kModulus)
+    return MLH_ERR_INVALID;
+  if (!load_canonical(host_output, P.width, output) || !load_canonical(polys, L * D, co))
+    return MLH_ERR_VERIFY;
+  const mlh::HostSha256 saved = tr->sha;
+  const u128 inv2 = h_inv(2);
+  std::vector<u128> rs, pol(D + 1);
+  u128 claim = h_load(sum), r = 0;
+  for (uint32_t k = 0; k < L; ++k) {  // sumcheck.rs:98-116
+    u128 sc = 0;
+    for (uint32_t j = 0; j < D; ++j) {
+      mlh_transcript_absorb(tr, polys + 16ull * (k * D + j), 16);
+      pol[j + 1] = co[k * D + j];
+      sc = h_add(sc, pol[j + 1]);
+    }
+    pol[0] = h_mul(h_sub(claim, sc), inv2);  // to_polynomial (:269-276)
+    uint8_t c[16];
+    mlh_transcript_next_challenge(tr, c);
+    r = h_load(c);
+    rs.push_back(r);
+    claim = horner(pol, r);
+  }
+  u128 delta = 1;  // Delta::evaluate (evaluation.rs:80-90)
+  for (uint32_t i = 0; i < L; ++i)
+    delta = h_mul(delta, h_add(h_mul(row[i], rs[i]), h_mul(h_sub(1, row[i]), h_sub(1, rs[i]))));
+  const u128 comp = cs_host_eval(P, output.data(), rnd.data(), mask.data());
+  if (h_mul(delta, comp) != claim) {  // :119-123
+    tr->sha = saved;
+    return MLH_ERR_VERIFY;
+  }
+  return MLH_OK;
 }
 
 }  // extern "C"
