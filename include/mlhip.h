@@ -607,6 +607,82 @@ mlh_status mlh_cs_sumcheck_verify(const mlh_cs_program* prog, uint32_t log_heigh
                                   const uint8_t* polys, const uint8_t* host_output,
                                   mlh_transcript* tr);
 
+/* ---- trace commitment and the system proof (src/constraint_system) -------- *
+ * The reference calls Commitment::new(&trace) in System::prover before the
+ * challenges are drawn (system.rs:62-63) and leaves its body a TODO
+ * (trace.rs:40-48).  Here the commitment is the commit phase of the batched
+ * PCS over the trace's width column MLEs, and the system proof opens it at
+ * the sumcheck's point, so a verifier without the trace can check
+ * sum_i delta[i] * composition(row_i) = sum.  Transcript order, prover and
+ * verifier alike:
+ *   1. absorb the 32-byte trace root;
+ *   2. ChallengeSet::new and the constraint mask (mlh_system_challenges);
+ *   3. the constraint sumcheck with delta = mlh_eq_table(row): per round
+ *      absorb c1..cD, draw r; output = Trace::evaluate(rs);
+ *   4. BatchedPCSProof::prove / verify with inputs = rs, outputs = output. */
+/* Row-major 2^log_height x width trace -> width column MLEs, column-major:
+ * out[j * 2^log_height + i] = matrix[i * width + j] (the columns
+ * Trace::evaluate, evaluation.rs:31-48, treats as MLEs).  Out of place: width
+ * 1..32, log_height 0..32; MLH_ERR_INVALID for a null pointer, a width out of
+ * range or overlapping buffers.  One kernel launch on the context stream. */
+mlh_status mlh_trace_columns(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                             uint32_t width, void* dev_out);
+/* Launch shape of mlh_trace_columns: the rows a block stages per tile and the
+ * number of blocks; a block visits ceil(tiles / blocks) tiles of
+ * min(tile_rows, 2^log_height) rows. */
+mlh_status mlh_trace_columns_launch_info(uint32_t log_height, uint32_t width, uint32_t* tile_rows,
+                                         uint32_t* blocks);
+/* Commitment::new (trace.rs:44-47): mlh_trace_columns, then the
+ * transcript-independent front of BatchedPCSProof::prove -- per column
+ * to_coefficient, bit reverse, reed_solomon at blow-up 2
+ * (batched_pcs.rs:135-149) -- and the batch layer's Merkle tree over the width
+ * codes (BatchedFriProverData::init, batched_fri.rs:41-81).  The handle owns
+ * the column evaluations (width * 2^log_height * 16 B), the codes (twice
+ * that) and the tree (mlh_merkle_layers_bytes(2^log_height)); dev_matrix is
+ * not modified and not referenced after the call.  Its root equals the
+ * batch_commitment of mlh_batched_pcs_prove over the same columns.  width
+ * 1..32, log_height 1..32 (the batched PCS needs one variable).  Synchronises. */
+typedef struct mlh_trace_commitment mlh_trace_commitment;
+mlh_status mlh_trace_commit(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                            uint32_t width, mlh_trace_commitment** out);
+mlh_status mlh_trace_commitment_root(const mlh_trace_commitment* c, uint8_t out[32]);
+uint32_t mlh_trace_commitment_width(const mlh_trace_commitment* c);
+uint32_t mlh_trace_commitment_log_height(const mlh_trace_commitment* c);
+/* Drains the context stream first. */
+void mlh_trace_commitment_destroy(mlh_trace_commitment* c);
+typedef struct mlh_system_proof {
+  uint32_t log_height, width, degree;
+  uint8_t* sumcheck_polys;   /* [log_height][degree+1][16], c1..cD per round  */
+  uint8_t* output;           /* [width][16] = Trace::evaluate(rs)             */
+  mlh_batched_pcs_proof pcs; /* caller-allocated as for mlh_batched_pcs_prove
+                                (n_vars = log_height, num_polys = width);
+                                pcs.fri.batch_commitment is the trace commitment */
+} mlh_system_proof;
+/* System::prover (system.rs:56-72) through to a proof, in the order above:
+ * the rounds of mlh_cs_sumcheck_prove (sumcheck.rs:40-53) on dev_matrix --
+ * the committed trace, folded in place -- then BatchedPCSProof::prove
+ * (batched_pcs.rs:150-180) on the handle's codes, evaluations and batch tree
+ * (no code or tree is computed a second time).  MLH_ERR_INVALID for a null
+ * pointer (proof->sumcheck_polys and proof->output included), a program width
+ * other than the commitment's, a handle of another context or a
+ * non-canonical sum.  On any non-OK return the transcript is exactly as it
+ * was at entry.  A dev_matrix that is not the committed trace cannot be
+ * detected here: the call returns MLH_OK and mlh_system_verify rejects the
+ * proof. */
+mlh_status mlh_system_prove(mlh_ctx* ctx, const mlh_cs_program* prog,
+                            const mlh_trace_commitment* commitment, void* dev_matrix,
+                            const uint8_t sum[16], mlh_transcript* tr, mlh_system_proof* proof);
+/* The verifier of that proof, host only: absorb pcs.fri.batch_commitment,
+ * draw the challenges (system.rs:39-54), System::verify_with_evaluations
+ * (sumcheck.rs:91-124) with host_output = proof->output, then
+ * BatchedPCSProof::verify (batched_pcs.rs:182-250) at the rs the sumcheck
+ * derived.  MLH_ERR_VERIFY where a component rejects, where
+ * proof->{log_height, width, degree} disagree with log_height or the program,
+ * and for a non-canonical element; the transcript is then exactly as it was
+ * at entry.  On MLH_OK it ends in the prover's state. */
+mlh_status mlh_system_verify(const mlh_cs_program* prog, uint32_t log_height, const uint8_t sum[16],
+                             const mlh_system_proof* proof, mlh_transcript* tr);
+
 /* ---- multilinear PCS (src/fri/multilinear_pcs.rs) ------------------------ */
 typedef struct mlh_pcs_proof {
   mlh_fri_proof fri;

@@ -73,6 +73,17 @@ class BatchedPcsProofC(ctypes.Structure):
     _fields_ = [("fri", BatchedFriProofC), ("sumcheck_polys", ctypes.c_void_p)]
 
 
+class SystemProofC(ctypes.Structure):
+    _fields_ = [
+        ("log_height", ctypes.c_uint32),
+        ("width", ctypes.c_uint32),
+        ("degree", ctypes.c_uint32),
+        ("sumcheck_polys", ctypes.c_void_p),
+        ("output", ctypes.c_void_p),
+        ("pcs", BatchedPcsProofC),
+    ]
+
+
 # mlh_transport (include/mlhip.h): collectives as C callbacks
 ALL_TO_ALL_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_uint64, ctypes.c_void_p)
@@ -216,6 +227,15 @@ SIGNATURES = {
     "mlh_cs_fold_and_sums": (_I, [_P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P]),
     "mlh_cs_sumcheck_prove": (_I, [_P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P]),
     "mlh_cs_sumcheck_verify": (_I, [_P, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "mlh_trace_columns": (_I, [_P, _P, _U32, _U32, _P]),
+    "mlh_trace_columns_launch_info": (_I, [_U32, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "mlh_trace_commit": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(_P)]),
+    "mlh_trace_commitment_root": (_I, [_P, _P]),
+    "mlh_trace_commitment_width": (_U32, [_P]),
+    "mlh_trace_commitment_log_height": (_U32, [_P]),
+    "mlh_trace_commitment_destroy": (None, [_P]),
+    "mlh_system_prove": (_I, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(SystemProofC)]),
+    "mlh_system_verify": (_I, [_P, _U32, _P, ctypes.POINTER(SystemProofC), _P]),
     "mlh_pcs_prove": (_I, [_P, _P, _U32, _P, _P, _P, ctypes.POINTER(PcsProofC)]),
     "mlh_pcs_verify": (_I, [ctypes.POINTER(PcsProofC), _U32, _P, _P, _P]),
     "mlh_bench_ntt": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(ctypes.c_float)]),

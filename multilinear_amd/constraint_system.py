@@ -6,13 +6,18 @@ The reference's ``Expr<F>(fn(&[F], &[F]) -> F)`` (constraints.rs:3-10) becomes
 a constraint program: expressions built here from ``var(j)``, ``rand(k)``,
 integers and ``+ - *`` compile to the straight-line wire format of
 include/mlhip.h, which libmlhip validates, interprets on the device (prover)
-and on the host (verifier).  ``Commitment`` is a placeholder in the reference
-(trace.rs:41-48) and has no counterpart here.
+and on the host (verifier).  ``Commitment`` is a TODO in the reference
+(trace.rs:41-48); here it is the commit phase of the batched PCS over the
+trace's columns (mlh_trace_commit), and ``System.committed_prover`` /
+``System.prove`` / ``SystemProof.verify`` compose it with the sumcheck into a
+proof a verifier checks without the trace (mlh_system_prove / _verify).
 """
 import ctypes
 import struct
 
-from .device import M, check, context, fe_bytes, fe_from_bytes, lib, ptr
+from . import _lib
+from .batched import BatchedPCSProof
+from .device import M, check, context, empty, fe_bytes, fe_from_bytes, lib, ptr
 from .polynomials import eq_table
 from .transcript import Transcript
 
@@ -260,6 +265,94 @@ class Trace:
         return _split(out, self._width)
 
 
+def trace_columns(dev_matrix, width, device=0):
+    """The row-major (height * width, 4) trace as its width column MLEs,
+    column-major: a new tensor, column j at rows [j * height, (j + 1) * height)
+    (mlh_trace_columns)."""
+    n = dev_matrix.shape[0]
+    assert width >= 1 and n % width == 0
+    height = n // width
+    assert height & (height - 1) == 0 and height > 0
+    ctx = context(device)
+    out = empty(n, device)
+    check(lib().mlh_trace_columns(ctx, ptr(dev_matrix), height.bit_length() - 1, width, ptr(out)),
+          ctx)
+    return out
+
+
+class Commitment:
+    """trace.rs:40-48 made real: the batched-PCS commit phase over the trace's
+    columns (mlh_trace_commitment).  Owns the column evaluations, the RS codes
+    and the batch tree on the device; the trace is not modified."""
+
+    def __init__(self, handle, device):
+        self.h = handle
+        self._device = device
+        self.width = lib().mlh_trace_commitment_width(handle)
+        self.log_height = lib().mlh_trace_commitment_log_height(handle)
+
+    def __del__(self):
+        try:
+            lib().mlh_trace_commitment_destroy(self.h)
+        except Exception:
+            pass
+
+    @staticmethod
+    def new(trace, device=0):  # trace.rs:44-47
+        ctx = context(device)
+        h = ctypes.c_void_p()
+        check(lib().mlh_trace_commit(ctx, ptr(trace.matrix()), trace.height().bit_length() - 1,
+                                     trace.width(), ctypes.byref(h)), ctx)
+        return Commitment(h.value, device)
+
+    def root(self):
+        out = (ctypes.c_uint8 * 32)()
+        check(lib().mlh_trace_commitment_root(self.h, out))
+        return bytes(out)
+
+
+class SystemProof:
+    """mlh_system_proof: the sumcheck polynomials, Trace::evaluate(rs) and the
+    batched-PCS opening of the committed columns at rs."""
+
+    def __init__(self, log_height, width, degree):
+        self.log_height, self.width, self.degree = log_height, width, degree
+        self._polys = (ctypes.c_uint8 * (16 * (degree + 1) * log_height))()
+        self._output = (ctypes.c_uint8 * (16 * width))()
+        self.pcs = BatchedPCSProof(log_height, width)
+        self.c = _lib.SystemProofC()
+        self.c.log_height, self.c.width, self.c.degree = log_height, width, degree
+        self.c.sumcheck_polys = ctypes.cast(self._polys, ctypes.c_void_p)
+        self.c.output = ctypes.cast(self._output, ctypes.c_void_p)
+        self.c.pcs = self.pcs.c
+
+    def _sync(self):  # the struct holds copies of the nested ones
+        self.pcs.c = self.c.pcs
+        self.pcs.fri_proof.c = self.c.pcs.fri
+
+    @property
+    def sumcheck_polynomials(self):
+        D = self.degree + 1
+        flat = _split(self._polys, D * self.log_height)
+        return [flat[D * k:D * k + D] for k in range(self.log_height)]
+
+    @property
+    def output(self):
+        return _split(self._output, self.width)
+
+    @property
+    def commitment(self):
+        return bytes(self.c.pcs.fri.batch_commitment)
+
+    def verify(self, transcript, constraints, layout, total_sum):
+        """mlh_system_verify, host only: True iff accepted.  The transcript
+        is the one the prover started from; it is advanced only on True."""
+        prog = Program(compile_program(constraints.constraints(), layout.columns, layout.randoms,
+                                       constraints.degree()))
+        return lib().mlh_system_verify(prog.h, self.log_height, fe_bytes(total_sum),
+                                       ctypes.byref(self.c), transcript.h) == 0
+
+
 class ChallengeSet:
     """system.rs:32-36,131-159, with the constraint mask of System::new
     (:90-95) from the same call (mlh_system_challenges)."""
@@ -305,6 +398,7 @@ class System:
         self._layout = layout
         self._trace = trace
         self._device = device
+        self._commitment = None
         n = len(constraints.constraints())
         self._challenges = ChallengeSet(transcript, layout.randoms, n, log_num_rows)
         self._constraint_mask = self._challenges.mask
@@ -315,6 +409,39 @@ class System:
     def prover(transcript, constraints, layout, trace, device=0):  # system.rs:56-72
         return System(transcript, constraints, layout, trace.height().bit_length() - 1, trace,
                       device)
+
+    @staticmethod
+    def committed_prover(transcript, constraints, layout, trace, device=0):
+        """system.rs:56-72 with the commitment made: commits to the trace, and
+        draws the challenges after the root on a clone of ``transcript``, which
+        is left as it was -- ``prove`` absorbs the root into it.  (``prover``
+        keeps the reference's behaviour, where Commitment::new is a TODO and
+        nothing is absorbed.)"""
+        com = Commitment.new(trace, device)
+        t = transcript.clone()
+        t.absorb(com.root())
+        s = System(t, constraints, layout, trace.height().bit_length() - 1, trace, device)
+        s._commitment = com
+        s._entry = transcript.random()
+        return s
+
+    def commitment(self):
+        return self._commitment
+
+    def prove(self, transcript, total_sum):
+        """mlh_system_prove on a clone of the trace's matrix: root, challenges,
+        sumcheck, opening.  ``transcript`` must be in the state
+        ``committed_prover`` saw."""
+        if transcript.random() != self._entry:
+            raise ValueError("prove needs the transcript in the state committed_prover was given")
+        ctx = context(self._device)
+        com, t = self._commitment, self._trace
+        p = SystemProof(com.log_height, com.width, self._constraints.degree())
+        work = t.matrix().clone()
+        check(lib().mlh_system_prove(ctx, self.program.h, com.h, ptr(work), fe_bytes(total_sum),
+                                     transcript.h, ctypes.byref(p.c)), ctx)
+        p._sync()
+        return p
 
     @staticmethod
     def verifier(transcript, constraints, layout, log_num_rows, device=0):  # system.rs:39-54

@@ -37,6 +37,7 @@
 #include "ntt.hpp"
 #include "sha256.hpp"
 #include "sumcheck.hpp"
+#include "trace_commit.hpp"
 #include "transcript_dev.hpp"
 
 using namespace mlh;
@@ -947,6 +948,7 @@ struct FriDevLoop {
   const fe* codes = nullptr;
   uint32_t m = 0;
   PoolBuf btree;
+  const uint8_t* bt = nullptr;  // the batch-layer tree: btree, or the caller's built one
   explicit FriDevLoop(mlh_ctx* c, mlh_fri_prover* pr) : ctx(c), p(pr), scratch(c), btree(c) {}
   uint8_t* sb() const { return scratch.as<uint8_t>(); }
   DevSha* dt() const { return reinterpret_cast<DevSha*>(sb()); }
@@ -983,16 +985,26 @@ struct FriDevLoop {
   // BatchedFriProverData::init (batched_fri.rs:41-98): batch layer over the
   // m codes' RS pairs, absorb its root, fingerprint_r = next_challenge(),
   // absorb LE16(fingerprint_r); r_0 = next_challenge() if challenge_r0.
+  // built_tree (optional): the batch layer's tree over these codes, already
+  // built (a trace commitment's); only its root is absorbed then.
   mlh_status init_batched(const fe* dev_codes, uint32_t num_codes, uint32_t log_code,
-                          const mlh_transcript* tr, bool challenge_r0, size_t n_extra = 0) {
+                          const mlh_transcript* tr, bool challenge_r0, size_t n_extra = 0,
+                          const uint8_t* built_tree = nullptr) {
     MLH_TRY(layout(log_code, tr, n_extra));
     codes = dev_codes;
     m = num_codes;
     const uint64_t N = 1ull << log_code, L = N / 2;
-    MLH_TRY(btree.alloc(mlh_merkle_layers_bytes(L)));
-    uint8_t* bt = btree.as<uint8_t>();
-    HIP_TRY(ctx, launch_batch_pairs_leaves(codes, m, N, bt, ctx->stream));
-    HIP_TRY(ctx, launch_merkle_levels(bt, L, ctx->stream, RootAbsorb{dt(), fr(), sb() + off_broot}));
+    if (built_tree) {
+      bt = built_tree;
+      HIP_TRY(ctx, launch_transcript_absorb(dt(), bt + (2 * L - 2) * 32, 32, fr(), ctx->stream,
+                                            sb() + off_broot));
+    } else {
+      MLH_TRY(btree.alloc(mlh_merkle_layers_bytes(L)));
+      uint8_t* t = btree.as<uint8_t>();
+      bt = t;
+      HIP_TRY(ctx, launch_batch_pairs_leaves(codes, m, N, t, ctx->stream));
+      HIP_TRY(ctx, launch_merkle_levels(t, L, ctx->stream, RootAbsorb{dt(), fr(), sb() + off_broot}));
+    }
     HIP_TRY(ctx, launch_transcript_absorb(dt(), reinterpret_cast<const uint8_t*>(fr()), 16,
                                           challenge_r0 ? r(0) : nullptr, ctx->stream));
     return MLH_OK;
@@ -2221,7 +2233,7 @@ static mlh_status batched_queries(mlh_ctx* ctx, FriDevLoop& lp, mlh_transcript* 
   MLH_TRY(query_stage(ctx, MLH_NUM_QUERIES * qbytes, &h));
   mlh::QueryIdx qi;
   memcpy(qi.v, idx.data(), 8ull * MLH_NUM_QUERIES);
-  HIP_TRY(ctx, launch_batch_queries(lp.codes, m, N, lp.btree.as<uint8_t>(), qi, MLH_NUM_QUERIES,
+  HIP_TRY(ctx, launch_batch_queries(lp.codes, m, N, lp.bt, qi, MLH_NUM_QUERIES,
                                     qbytes, h, ctx->stream));
   MLH_TRY(gather_queries_dev(ctx, lp.p, qi, nullptr, MLH_NUM_QUERIES, qbytes,
                              32ull * m + 32ull * (L - 1), h));
@@ -2424,30 +2436,41 @@ void mlh_batched_fri_prover_destroy(mlh_batched_fri_prover* bp) {
   }
 }
 
-mlh_status mlh_batched_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t num_polys,
-                                 uint32_t n_vars, const uint8_t* inputs, const uint8_t* outputs,
-                                 mlh_transcript* tr, mlh_batched_pcs_proof* proof) {
-  if (!ctx || !dev_evals || !inputs || !outputs || !tr || !proof)
-    return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (num_polys == 0) return fail(ctx, MLH_ERR_INVALID, "no polynomials");
-  if (n_vars < 1 || n_vars > 36) return fail(ctx, MLH_ERR_INVALID, "n_vars out of range");
-  const uint32_t log_domain = n_vars + MLH_LOG_BLOWUP;
+}  // extern "C"
+
+// The transcript-independent front of BatchedPCSProof::prove
+// (batched_pcs.rs:135-149): per polynomial to_coefficient, bit reverse and
+// reed_solomon at blow-up 2, into dev_codes ([num_polys][2^(n_vars+1)]).
+static mlh_status batched_pcs_codes(mlh_ctx* ctx, const void* dev_evals, uint32_t num_polys,
+                                    uint32_t n_vars, fe* dev_codes) {
   const uint64_t n = 1ull << n_vars, N = 2 * n;
   uint8_t genb[16];
-  h_store(genb, h_pow2_generator(log_domain));
-  // codes: to_coefficient, bit reverse, RS per polynomial (batched_pcs.rs:137-146)
-  PoolBuf coeffs(ctx), codes(ctx), matrix(ctx), outs(ctx);
+  h_store(genb, h_pow2_generator(n_vars + MLH_LOG_BLOWUP));
+  PoolBuf coeffs(ctx);
   MLH_TRY(coeffs.alloc(n * 16));
-  MLH_TRY(codes.alloc((uint64_t)num_polys * N * 16));
-  MLH_TRY(matrix.alloc(n * 16));
-  MLH_TRY(outs.alloc(16ull * num_polys));
   const uint8_t* ev = reinterpret_cast<const uint8_t*>(dev_evals);
   for (uint32_t j = 0; j < num_polys; ++j) {
     HIP_TRY(ctx, launch_mobius(coeffs.as<fe>(), n_vars, false, ctx->stream,
                                reinterpret_cast<const fe*>(ev + (uint64_t)j * n * 16)));
     MLH_TRY(mlh_reed_solomon_brev(ctx, coeffs.p, n_vars, genb,
-                                  codes.as<uint8_t>() + (uint64_t)j * N * 16));
+                                  reinterpret_cast<uint8_t*>(dev_codes) + (uint64_t)j * N * 16));
   }
+  return MLH_OK;
+}
+
+// BatchedPCSProof::prove from the point where the codes exist
+// (batched_pcs.rs:150-180): dev_codes as batched_pcs_codes leaves them,
+// dev_evals the MLEs; built_tree (optional) the batch layer's tree over those
+// codes (FriDevLoop::init_batched).
+static mlh_status batched_pcs_open(mlh_ctx* ctx, const fe* dev_codes, const void* dev_evals,
+                                   const uint8_t* built_tree, uint32_t num_polys, uint32_t n_vars,
+                                   const uint8_t* inputs, const uint8_t* outputs,
+                                   mlh_transcript* tr, mlh_batched_pcs_proof* proof) {
+  const uint32_t log_domain = n_vars + MLH_LOG_BLOWUP;
+  const uint64_t n = 1ull << n_vars;
+  PoolBuf matrix(ctx), outs(ctx);
+  MLH_TRY(matrix.alloc(n * 16));
+  MLH_TRY(outs.alloc(16ull * num_polys));
   // init (batched_pcs.rs:36-78): absorb the claim, batched FRI init.  The
   // replay check is armed first: any failure from here on restores the
   // caller's transcript to its state at entry.
@@ -2460,7 +2483,7 @@ mlh_status mlh_batched_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t n
   FriDevLoop lp(ctx, fp.get());
   device_arm(ctx);
   const bool fused = n_vars <= ctx->pcs_fused_max;
-  MLH_TRY(lp.init_batched(codes.as<fe>(), num_polys, log_domain, tr, false, fused ? 5 : 0));
+  MLH_TRY(lp.init_batched(dev_codes, num_polys, log_domain, tr, false, fused ? 5 : 0, built_tree));
   // fingerprinted MLE + eq table; previous_sum = fingerprint(fr, outputs)
   HIP_TRY(ctx, launch_fingerprint(reinterpret_cast<const fe*>(dev_evals), num_polys, n, lp.fr(),
                                   matrix.as<fe>(), ctx->stream));
@@ -2523,6 +2546,117 @@ mlh_status mlh_batched_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t n
   MLH_TRY(rc.status());
   memcpy(proof->fri.batch_commitment, lp.host_broot(), 32);
   return batched_queries(ctx, lp, tr, &proof->fri);
+}
+
+extern "C" {
+
+mlh_status mlh_batched_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t num_polys,
+                                 uint32_t n_vars, const uint8_t* inputs, const uint8_t* outputs,
+                                 mlh_transcript* tr, mlh_batched_pcs_proof* proof) {
+  if (!ctx || !dev_evals || !inputs || !outputs || !tr || !proof)
+    return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (num_polys == 0) return fail(ctx, MLH_ERR_INVALID, "no polynomials");
+  if (n_vars < 1 || n_vars > 36) return fail(ctx, MLH_ERR_INVALID, "n_vars out of range");
+  PoolBuf codes(ctx);
+  MLH_TRY(codes.alloc(((uint64_t)num_polys << (n_vars + MLH_LOG_BLOWUP)) * 16));
+  MLH_TRY(batched_pcs_codes(ctx, dev_evals, num_polys, n_vars, codes.as<fe>()));
+  return batched_pcs_open(ctx, codes.as<fe>(), dev_evals, nullptr, num_polys, n_vars, inputs,
+                          outputs, tr, proof);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// trace commitment and the system proof (constraint_system/trace.rs:40-48,
+// system.rs:56-72): Commitment::new as the commit phase of the batched PCS
+// over the trace's column MLEs, opened at the sumcheck's point.
+// ---------------------------------------------------------------------------
+struct mlh_trace_commitment {
+  mlh_ctx* ctx;
+  uint32_t log_height = 0, width = 0;
+  void* evals = nullptr;  // [width][2^log_height] column MLEs
+  void* codes = nullptr;  // [width][2^(log_height+1)] RS codes
+  void* tree = nullptr;   // batch layer: 2^log_height leaves + levels
+  uint8_t root[32];
+  ~mlh_trace_commitment() {
+    pool_free(ctx, evals);
+    pool_free(ctx, codes);
+    pool_free(ctx, tree);
+  }
+};
+
+static bool ranges_overlap(const void* a, const void* b, uint64_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y ? y - x < bytes : x - y < bytes;
+}
+
+extern "C" {
+
+mlh_status mlh_trace_columns(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                             uint32_t width, void* dev_out) {
+  if (!ctx || !dev_matrix || !dev_out) return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (width < 1 || width > kCsMaxWidth || log_height > kCsMaxLogHeight)
+    return fail(ctx, MLH_ERR_INVALID, "width 1..32, log_height 0..32");
+  if (ranges_overlap(dev_matrix, dev_out, ((uint64_t)width << log_height) * 16))
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_columns is out of place: the buffers overlap");
+  ProfScope ps(ctx, "trace_columns");
+  HIP_TRY(ctx, launch_trace_columns(reinterpret_cast<const fe*>(dev_matrix),
+                                    reinterpret_cast<fe*>(dev_out), log_height, width, ctx->stream));
+  ps.end();
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_columns_launch_info(uint32_t log_height, uint32_t width, uint32_t* tile_rows,
+                                         uint32_t* blocks) {
+  if (!tile_rows || !blocks || width < 1 || width > kCsMaxWidth || log_height > kCsMaxLogHeight)
+    return MLH_ERR_INVALID;
+  *tile_rows = tc_tile_rows(width);
+  *blocks = tc_blocks(1ull << log_height, width);
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_commit(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                            uint32_t width, mlh_trace_commitment** out) {
+  if (!ctx || !dev_matrix || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (width < 1 || width > kCsMaxWidth || log_height < 1 || log_height > kCsMaxLogHeight)
+    return fail(ctx, MLH_ERR_INVALID, "width 1..32, log_height 1..32");
+  std::unique_ptr<mlh_trace_commitment> c(new mlh_trace_commitment());
+  c->ctx = ctx;
+  c->log_height = log_height;
+  c->width = width;
+  const uint64_t n = 1ull << log_height;
+  MLH_TRY(pool_alloc(ctx, width * n * 16, &c->evals));
+  MLH_TRY(pool_alloc(ctx, width * n * 32, &c->codes));
+  MLH_TRY(pool_alloc(ctx, mlh_merkle_layers_bytes(n), &c->tree));
+  MLH_TRY(mlh_trace_columns(ctx, dev_matrix, log_height, width, c->evals));
+  fe* codes = reinterpret_cast<fe*>(c->codes);
+  MLH_TRY(batched_pcs_codes(ctx, c->evals, width, log_height, codes));
+  // the batch layer of BatchedFriProverData::init (batched_fri.rs:41-81)
+  uint8_t* bt = reinterpret_cast<uint8_t*>(c->tree);
+  HIP_TRY(ctx, launch_batch_pairs_leaves(codes, width, 2 * n, bt, ctx->stream));
+  HIP_TRY(ctx, launch_merkle_levels(bt, n, ctx->stream));
+  MLH_TRY(read_root(ctx, bt, n, c->root));
+  *out = c.release();
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_commitment_root(const mlh_trace_commitment* c, uint8_t out[32]) {
+  if (!c || !out) return MLH_ERR_INVALID;
+  memcpy(out, c->root, 32);
+  return MLH_OK;
+}
+
+uint32_t mlh_trace_commitment_width(const mlh_trace_commitment* c) { return c ? c->width : 0; }
+
+uint32_t mlh_trace_commitment_log_height(const mlh_trace_commitment* c) {
+  return c ? c->log_height : 0;
+}
+
+void mlh_trace_commitment_destroy(mlh_trace_commitment* c) {
+  if (c) {
+    (void)hipStreamSynchronize(c->ctx->stream);
+    delete c;
+  }
 }
 
 }  // extern "C"
@@ -2847,6 +2981,83 @@ mlh_status mlh_cs_sumcheck_prove(mlh_ctx* ctx, const mlh_cs_program* prog, uint3
   MLH_TRY(rc.status());
   if (polys_out) memcpy(polys_out, host.data(), 16ull * D * L);
   if (rs_out) memcpy(rs_out, host.data() + 16ull * D * L, 16ull * L);
+  return MLH_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// System::prover + the composed proof (system.rs:56-72): commitment root ->
+// ChallengeSet -> constraint sumcheck -> batched PCS opening of the committed
+// columns at the sumcheck's point.
+// ---------------------------------------------------------------------------
+// Restores the caller's transcript to its state at construction unless keep()
+// was called: a failed prove leaves it untouched (mlhip.h), the root absorbed
+// first included.
+struct TranscriptGuard {
+  mlh_transcript* tr;
+  mlh::HostSha256 saved;
+  bool kept = false;
+  explicit TranscriptGuard(mlh_transcript* t) : tr(t), saved(t->sha) {}
+  TranscriptGuard(const TranscriptGuard&) = delete;
+  TranscriptGuard& operator=(const TranscriptGuard&) = delete;
+  ~TranscriptGuard() {
+    if (!kept) tr->sha = saved;
+  }
+  void keep() { kept = true; }
+};
+
+extern "C" {
+
+mlh_status mlh_system_prove(mlh_ctx* ctx, const mlh_cs_program* prog,
+                            const mlh_trace_commitment* com, void* dev_matrix,
+                            const uint8_t sum[16], mlh_transcript* tr, mlh_system_proof* proof) {
+  if (!ctx || !prog || !com || !dev_matrix || !sum || !tr || !proof || !proof->sumcheck_polys ||
+      !proof->output)
+    return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (com->ctx != ctx) return fail(ctx, MLH_ERR_INVALID, "commitment of another context");
+  if (prog->p.width != com->width)
+    return fail(ctx, MLH_ERR_INVALID, "program width differs from the commitment's");
+  if (h_load(sum) >= kModulus) return fail(ctx, MLH_ERR_INVALID, "non-canonical sum");
+  const CsProgram& P = prog->p;
+  const uint32_t L = com->log_height, W = com->width;
+  TranscriptGuard guard(tr);
+  // 1. the commitment, where system.rs:62-63 makes it; 2. ChallengeSet::new
+  mlh_transcript_absorb(tr, com->root, 32);
+  uint32_t log_nc = 0;
+  while ((1ull << log_nc) < P.n_constraints) ++log_nc;
+  std::vector<uint8_t> row(16ull * L), rnd(16ull * P.n_randoms + 16), cons(16ull * log_nc + 16),
+      mask(16ull * P.n_constraints), rs(16ull * L);
+  if (mlh_system_challenges(tr, L, P.n_randoms, P.n_constraints, row.data(), rnd.data(),
+                            cons.data(), mask.data()) != MLH_OK)
+    return fail(ctx, MLH_ERR_INVALID, "challenge set");
+  // 3. delta = eq(row), the sumcheck rounds; output = row 0 of the folded matrix
+  PoolBuf delta(ctx);
+  MLH_TRY(delta.alloc(16ull << L));
+  MLH_TRY(mlh_eq_table(ctx, row.data(), L, delta.p));
+  {
+    ProfScope ps(ctx, "system_sumcheck");
+    MLH_TRY(mlh_cs_sumcheck_prove(ctx, prog, W, dev_matrix, delta.p, L, rnd.data(), mask.data(), sum,
+                                  tr, proof->sumcheck_polys, rs.data()));
+    ps.end();
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev_matrix, 16ull * W, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<uint8_t> output(ctx->pinned, ctx->pinned + 16ull * W);
+  // 4. BatchedPCSProof::prove(inputs = rs, outputs = output) on the committed
+  // codes, evaluations and batch tree
+  {
+    ProfScope ps(ctx, "system_open");
+    MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com->codes), com->evals,
+                             reinterpret_cast<const uint8_t*>(com->tree), W, L, rs.data(),
+                             output.data(), tr, &proof->pcs));
+    ps.end();
+  }
+  memcpy(proof->output, output.data(), output.size());
+  proof->log_height = L;
+  proof->width = W;
+  proof->degree = P.degree;
+  guard.keep();
   return MLH_OK;
 }
 

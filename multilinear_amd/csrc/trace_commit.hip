@@ -1,0 +1,79 @@
+// Trace commitment kernel: the row-major 2^L x W trace as W column MLEs
+// (column-major), the input of the batched PCS commit that stands for
+// Commitment::new (constraint_system/trace.rs:40-48).
+//
+// trace_columns_kernel: a block takes tiles of R consecutive rows (R a power
+// of two, R * W <= 2048 elements; a table shorter than R is one short tile).
+// A tile's rows * W elements are contiguous in the trace: lane e loads element
+// e of the tile (global_load_dwordx4, coalesced), at most 8 loads per lane all
+// issued before the first use, and stores it to the LDS slot j * pitch + i of
+// its (row i, column j) (ds_write_b128; pitch: trace_commit.hpp).  After a
+// barrier lane e reads slot (e / rows) * pitch + (e mod rows) -- consecutive
+// lanes read consecutive slots of one column -- and stores it to
+// out[j * H + row0 + i]: every column's run of `rows` elements is written as
+// contiguous 16-byte stores.  A block loops over tiles t = block, block +
+// grid, ...
+#include "trace_commit.hpp"
+
+namespace mlh {
+
+constexpr uint32_t kTcPerLane = kTcTileElems / kTcThreads;  // 8
+
+__global__ __launch_bounds__(kTcThreads) void trace_columns_kernel(
+    const uint4* __restrict__ in, uint4* __restrict__ out, uint64_t height, uint32_t width,
+    uint32_t log_rows, uint32_t pitch, uint64_t tiles) {
+  extern __shared__ uint4 tc_lds[];
+  const uint32_t rows = 1u << log_rows, n = rows * width;  // n <= kTcTileElems
+  const uint32_t lane = threadIdx.x;
+  // (row, column) of element `lane`, advanced by kTcThreads elements per step
+  const uint32_t i0 = lane / width, j0 = lane - i0 * width;
+  const uint32_t di = kTcThreads / width, dj = kTcThreads - di * width;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t row0 = t << log_rows;
+    const uint4* src = in + row0 * width;
+    uint4 v[kTcPerLane];
+#pragma unroll
+    for (uint32_t k = 0; k < kTcPerLane; ++k) {
+      const uint32_t e = lane + k * kTcThreads;
+      v[k] = e < n ? src[e] : uint4{0, 0, 0, 0};
+    }
+    uint32_t i = i0, j = j0;
+#pragma unroll
+    for (uint32_t k = 0; k < kTcPerLane; ++k) {
+      const uint32_t e = lane + k * kTcThreads;
+      if (e < n) tc_lds[j * pitch + i] = v[k];
+      i += di;
+      j += dj;
+      if (j >= width) {
+        j -= width;
+        ++i;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < kTcPerLane; ++k) {
+      const uint32_t e = lane + k * kTcThreads;
+      if (e < n) {
+        const uint32_t c = e >> log_rows, r = e & (rows - 1);
+        out[(uint64_t)c * height + row0 + r] = tc_lds[c * pitch + r];
+      }
+    }
+    __syncthreads();  // the next tile's stores reuse the slots
+  }
+}
+
+hipError_t launch_trace_columns(const fe* in, fe* out, uint32_t log_height, uint32_t width,
+                                hipStream_t st) {
+  const uint64_t height = 1ull << log_height;
+  const uint32_t R = tc_tile_rows(width);
+  uint32_t log_rows = 0;
+  while ((2ull << log_rows) <= (height < R ? height : R)) ++log_rows;  // rows = min(R, height)
+  const uint64_t tiles = height >> log_rows;
+  const uint32_t pitch = tc_pitch(width, R);
+  hipLaunchKernelGGL(trace_columns_kernel, dim3(tc_blocks(height, width)), dim3(kTcThreads),
+                     (size_t)width * pitch * sizeof(uint4), st, reinterpret_cast<const uint4*>(in),
+                     reinterpret_cast<uint4*>(out), height, width, log_rows, pitch, tiles);
+  return hipGetLastError();
+}
+
+}  // namespace mlh

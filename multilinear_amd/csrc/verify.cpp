@@ -466,11 +466,15 @@ mlh_status mlh_system_challenges(mlh_transcript* tr, uint32_t log_rows, uint32_t
   return MLH_OK;
 }
 
-mlh_status mlh_cs_sumcheck_verify(const mlh_cs_program* prog, uint32_t log_height,
-                                  const uint8_t* host_row_points, const uint8_t* host_randoms,
-                                  const uint8_t* host_mask, const uint8_t sum[16],
-                                  const uint8_t* polys, const uint8_t* host_output,
-                                  mlh_transcript* tr) {
+}  // extern "C"
+
+// System::verify_with_evaluations (sumcheck.rs:91-124); rs_out (optional)
+// receives the challenges it derives.
+static mlh_status cs_sumcheck_verify_rs(const mlh_cs_program* prog, uint32_t log_height,
+                                        const uint8_t* host_row_points, const uint8_t* host_randoms,
+                                        const uint8_t* host_mask, const uint8_t sum[16],
+                                        const uint8_t* polys, const uint8_t* host_output,
+                                        mlh_transcript* tr, std::vector<u128>* rs_out) {
   if (!prog || !host_row_points || !host_mask || !sum || !polys || !host_output || !tr ||
       log_height < 1 || log_height > kCsMaxLogHeight || (prog->p.n_randoms && !host_randoms))
     return MLH_ERR_INVALID;
@@ -505,6 +509,55 @@ mlh_status mlh_cs_sumcheck_verify(const mlh_cs_program* prog, uint32_t log_heigh
     delta = h_mul(delta, h_add(h_mul(row[i], rs[i]), h_mul(h_sub(1, row[i]), h_sub(1, rs[i]))));
   const u128 comp = cs_host_eval(P, output.data(), rnd.data(), mask.data());
   if (h_mul(delta, comp) != claim) {  // :119-123
+    tr->sha = saved;
+    return MLH_ERR_VERIFY;
+  }
+  if (rs_out) *rs_out = rs;
+  return MLH_OK;
+}
+
+extern "C" {
+
+mlh_status mlh_cs_sumcheck_verify(const mlh_cs_program* prog, uint32_t log_height,
+                                  const uint8_t* host_row_points, const uint8_t* host_randoms,
+                                  const uint8_t* host_mask, const uint8_t sum[16],
+                                  const uint8_t* polys, const uint8_t* host_output,
+                                  mlh_transcript* tr) {
+  return cs_sumcheck_verify_rs(prog, log_height, host_row_points, host_randoms, host_mask, sum,
+                               polys, host_output, tr, nullptr);
+}
+
+mlh_status mlh_system_verify(const mlh_cs_program* prog, uint32_t log_height, const uint8_t sum[16],
+                             const mlh_system_proof* proof, mlh_transcript* tr) {
+  if (!prog || !sum || !proof || !tr || !proof->sumcheck_polys || !proof->output ||
+      !proof->pcs.sumcheck_polys)
+    return MLH_ERR_INVALID;
+  const CsProgram& P = prog->p;
+  if (log_height < 1 || log_height > kCsMaxLogHeight || proof->log_height != log_height ||
+      proof->width != P.width || proof->degree != P.degree || proof->pcs.fri.num_codes != P.width ||
+      h_load(sum) >= kModulus)
+    return MLH_ERR_VERIFY;
+  const uint32_t L = log_height;
+  const mlh::HostSha256 saved = tr->sha;
+  // 1. the commitment; 2. the challenges (system.rs:39-54)
+  mlh_transcript_absorb(tr, proof->pcs.fri.batch_commitment, 32);
+  uint32_t log_nc = 0;
+  while ((1ull << log_nc) < P.n_constraints) ++log_nc;
+  std::vector<uint8_t> row(16ull * L), rnd(16ull * P.n_randoms + 16), cons(16ull * log_nc + 16),
+      mask(16ull * P.n_constraints);
+  mlh_status st = mlh_system_challenges(tr, L, P.n_randoms, P.n_constraints, row.data(), rnd.data(),
+                                        cons.data(), mask.data());
+  // 3. the sumcheck against the claimed output; 4. the opening at its rs
+  std::vector<u128> rs;
+  if (st == MLH_OK)
+    st = cs_sumcheck_verify_rs(prog, L, row.data(), rnd.data(), mask.data(), sum,
+                               proof->sumcheck_polys, proof->output, tr, &rs);
+  if (st == MLH_OK) {
+    std::vector<uint8_t> in(16ull * L);
+    for (uint32_t i = 0; i < L; ++i) h_store(in.data() + 16ull * i, rs[i]);
+    st = mlh_batched_pcs_verify(&proof->pcs, L, in.data(), proof->output, tr);
+  }
+  if (st != MLH_OK) {
     tr->sha = saved;
     return MLH_ERR_VERIFY;
   }
