@@ -112,6 +112,12 @@ mlh_status mlh_field_neg(mlh_ctx* ctx, const void* dev_a, void* dev_out, uint64_
 /* out[i] = a[i] * c (scalar Mul, field.rs:98-106); c canonical LE16. */
 mlh_status mlh_field_scale(mlh_ctx* ctx, const void* dev_a, const uint8_t c[16], void* dev_out,
                            uint64_t n);
+/* out[i] = a[i]^(M - 2): the inverse, zero -> zero, as Field128's Div through
+ * winter-math's inv (field.rs:113-118).  n = 0 is MLH_OK and does nothing;
+ * dev_out == dev_a (in place) is allowed, any other overlap is
+ * MLH_ERR_INVALID.  One power per thread over several elements (Montgomery's
+ * trick): about 3 + 138 / K products per element.  One launch. */
+mlh_status mlh_field_inv(mlh_ctx* ctx, const void* dev_a, void* dev_out, uint64_t n);
 
 /* ---- NTT (src/ntt/mod.rs) ------------------------------------------------ */
 /* Polynomial::ntt (ntt/mod.rs:69-110): evals[i] = sum_j coeffs[j] gen^(ij),
@@ -607,6 +613,29 @@ mlh_status mlh_cs_sumcheck_verify(const mlh_cs_program* prog, uint32_t log_heigh
                                   const uint8_t* polys, const uint8_t* host_output,
                                   mlh_transcript* tr);
 
+/* The same with sum columns (WitnessLayout::sum_columns, system.rs:27-29: "the
+ * sum of all sum columns is the main result of the trace"): the claim is
+ *   sum_i [ delta[i] composition(row_i) + beta sum_{j in S} row_i[j] ]
+ * with S = the set bits of sum_column_mask (bit j = column j; a bit at or
+ * above the width is MLH_ERR_INVALID) and claim = sum + beta * column_sum, which
+ * the caller forms.  The round polynomial keeps total degree d + 1 and its D
+ * points; the final check is delta(rs) composition(output) + beta
+ * sum_{j in S} output[j] = pol(r_last).  sum_column_mask = 0 (beta may be
+ * NULL) is mlh_cs_sumcheck_prove / _verify themselves, which call these: the
+ * same launches, the same bytes. */
+mlh_status mlh_cs_sumcheck_prove_sums(mlh_ctx* ctx, const mlh_cs_program* prog, uint32_t width,
+                                      void* dev_matrix, void* dev_delta, uint32_t log_height,
+                                      const uint8_t* host_randoms, const uint8_t* host_mask,
+                                      uint32_t sum_column_mask, const uint8_t* beta,
+                                      const uint8_t claim[16], mlh_transcript* tr,
+                                      uint8_t* polys_out, uint8_t* rs_out);
+mlh_status mlh_cs_sumcheck_verify_sums(const mlh_cs_program* prog, uint32_t log_height,
+                                       const uint8_t* host_row_points, const uint8_t* host_randoms,
+                                       const uint8_t* host_mask, uint32_t sum_column_mask,
+                                       const uint8_t* beta, const uint8_t claim[16],
+                                       const uint8_t* polys, const uint8_t* host_output,
+                                       mlh_transcript* tr);
+
 /* ---- trace commitment and the system proof (src/constraint_system) -------- *
  * The reference calls Commitment::new(&trace) in System::prover before the
  * challenges are drawn (system.rs:62-63) and leaves its body a TODO
@@ -645,6 +674,25 @@ mlh_status mlh_trace_columns_launch_info(uint32_t log_height, uint32_t width, ui
 typedef struct mlh_trace_commitment mlh_trace_commitment;
 mlh_status mlh_trace_commit(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
                             uint32_t width, mlh_trace_commitment** out);
+/* The same over columns [col0, col0 + ncols) of the row-major trace only:
+ * out[j * 2^log_height + i] = matrix[i * width + col0 + j], j < ncols.  No
+ * element outside the range is read (in phase 1 of a two-phase proof the later
+ * columns are not filled yet).  MLH_ERR_INVALID also for ncols = 0 or a range
+ * that leaves the trace.  One kernel launch; its launch shape is that of an
+ * ncols-wide trace. */
+mlh_status mlh_trace_columns_range(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                   uint32_t width, uint32_t col0, uint32_t ncols, void* dev_out);
+mlh_status mlh_trace_columns_range_launch_info(uint32_t log_height, uint32_t width, uint32_t col0,
+                                               uint32_t ncols, uint32_t* tile_rows,
+                                               uint32_t* blocks);
+/* mlh_trace_commit over columns [col0, col0 + ncols) (Commitment::new,
+ * trace.rs:44-47, of the columns a WitnessLayout phase holds, system.rs:23-26):
+ * the handle's width is ncols and its root equals the batch_commitment of
+ * mlh_batched_pcs_prove over those columns.  It depends on no element outside
+ * the range. */
+mlh_status mlh_trace_commit_range(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                  uint32_t width, uint32_t col0, uint32_t ncols,
+                                  mlh_trace_commitment** out);
 mlh_status mlh_trace_commitment_root(const mlh_trace_commitment* c, uint8_t out[32]);
 uint32_t mlh_trace_commitment_width(const mlh_trace_commitment* c);
 uint32_t mlh_trace_commitment_log_height(const mlh_trace_commitment* c);
@@ -682,6 +730,67 @@ mlh_status mlh_system_prove(mlh_ctx* ctx, const mlh_cs_program* prog,
  * at entry.  On MLH_OK it ends in the prover's state. */
 mlh_status mlh_system_verify(const mlh_cs_program* prog, uint32_t log_height, const uint8_t sum[16],
                              const mlh_system_proof* proof, mlh_transcript* tr);
+
+/* ---- the system proof in two phases (WitnessLayout, system.rs:17-30) ------- *
+ * pre_random_columns P (1 <= P <= width W): "the columns that you must fill
+ * before knowing the value of the random challenges" (system.rs:23-26);
+ * sum_columns S (a mask over the columns): "the sum of all sum columns is the
+ * main result of the trace" (system.rs:27-29).  The verifier checks
+ *   sum_i delta[i] composition(row_i) = sum  and  sum_i sum_{j in S} row_i[j]
+ *   = column_sum
+ * through one sumcheck over their random combination.  Transcript order:
+ *   1. absorb root1, the commitment to columns [0, P);
+ *   2. the trace randoms: n_randoms copies of one next_challenge()
+ *      (ChallengeSet::new, system.rs:139);
+ *   3. if P < W: absorb root2, the commitment to columns [P, W);
+ *   4. the row and constraint challenges and the mask (mlh_system_challenges
+ *      with n_randoms = 0);
+ *   5. if S is not empty: absorb LE16(column_sum), beta = next_challenge();
+ *   6. mlh_cs_sumcheck_prove_sums with claim = sum + beta * column_sum;
+ *      output = row 0 of the folded matrix;
+ *   7. BatchedPCSProof::prove (batched_pcs.rs:127-180) on commitment 1 with
+ *      inputs rs, outputs output[0:P];  8. if P < W: the same on commitment 2
+ *      with output[P:W].
+ * With P = W and S empty this is mlh_system_prove's order, byte for byte. */
+/* Steps 1-2 on a copy of tr, which is left as it is: what the prover calls
+ * between the two commitments to fill the columns at and above P.  out:
+ * n_randoms elements. */
+mlh_status mlh_system_trace_randoms(const mlh_transcript* tr, const uint8_t root1[32],
+                                    uint32_t n_randoms, uint8_t* out);
+typedef struct mlh_phased_proof {
+  uint32_t log_height, width, degree;
+  uint32_t pre_random_columns; /* P */
+  uint32_t sum_column_mask;    /* S, bit j = column j */
+  uint8_t* sumcheck_polys;     /* [log_height][degree+1][16], c1..cD per round */
+  uint8_t* output;             /* [width][16] = Trace::evaluate(rs)            */
+  /* caller-allocated as for mlh_batched_pcs_prove with n_vars = log_height:
+   * pcs[0] for P polynomials, pcs[1] for W - P (unused when P = W) */
+  mlh_batched_pcs_proof pcs[2];
+} mlh_phased_proof;
+/* System::prover (system.rs:56-72) for a two-phase layout, steps 1-8.  P is
+ * commitment1's width; commitment2 is NULL iff P = W, and the two widths add
+ * up to the program's.  dev_matrix is the trace as commitment2 saw it, folded
+ * in place.  Both openings run on the handles' codes, evaluations and batch
+ * trees (nothing is computed a second time).  MLH_ERR_INVALID for a null
+ * pointer, widths that do not add up, handles of different heights or of
+ * another context, a mask bit at or above W, a non-canonical sum or
+ * column_sum.  On any non-OK return the transcript is exactly as at entry. */
+mlh_status mlh_system_prove_phased(mlh_ctx* ctx, const mlh_cs_program* prog,
+                                   const mlh_trace_commitment* commitment1,
+                                   const mlh_trace_commitment* commitment2,
+                                   uint32_t sum_column_mask, void* dev_matrix,
+                                   const uint8_t sum[16], const uint8_t column_sum[16],
+                                   mlh_transcript* tr, mlh_phased_proof* proof);
+/* The verifier (system.rs:39-54, sumcheck.rs:91-124, batched_pcs.rs:182-250),
+ * host only, in the same order with root1 / root2 = pcs[0] / pcs[1]'s
+ * batch_commitment.  MLH_ERR_VERIFY, with the transcript exactly as at entry,
+ * for any rejection, any disagreement between the proof's header and
+ * (log_height, the program, pre_random_columns, sum_column_mask) and any
+ * non-canonical element.  On MLH_OK the transcript ends in the prover's state. */
+mlh_status mlh_system_verify_phased(const mlh_cs_program* prog, uint32_t log_height,
+                                    uint32_t pre_random_columns, uint32_t sum_column_mask,
+                                    const uint8_t sum[16], const uint8_t column_sum[16],
+                                    const mlh_phased_proof* proof, mlh_transcript* tr);
 
 /* ---- multilinear PCS (src/fri/multilinear_pcs.rs) ------------------------ */
 typedef struct mlh_pcs_proof {

@@ -84,6 +84,19 @@ class SystemProofC(ctypes.Structure):
     ]
 
 
+class PhasedProofC(ctypes.Structure):
+    _fields_ = [
+        ("log_height", ctypes.c_uint32),
+        ("width", ctypes.c_uint32),
+        ("degree", ctypes.c_uint32),
+        ("pre_random_columns", ctypes.c_uint32),
+        ("sum_column_mask", ctypes.c_uint32),
+        ("sumcheck_polys", ctypes.c_void_p),
+        ("output", ctypes.c_void_p),
+        ("pcs", BatchedPcsProofC * 2),
+    ]
+
+
 # mlh_transport (include/mlhip.h): collectives as C callbacks
 ALL_TO_ALL_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_uint64, ctypes.c_void_p)
@@ -133,6 +146,7 @@ SIGNATURES = {
     "mlh_field_mul": (_I, [_P, _P, _P, _P, _U64]),
     "mlh_field_neg": (_I, [_P, _P, _P, _U64]),
     "mlh_field_scale": (_I, [_P, _P, _P, _P, _U64]),
+    "mlh_field_inv": (_I, [_P, _P, _P, _U64]),
     "mlh_ntt": (_I, [_P, _P, _P, _U32, _P]),
     "mlh_intt": (_I, [_P, _P, _P, _U32, _P]),
     "mlh_bit_reverse_permutation": (_I, [_P, _P, _P, _U32]),
@@ -227,7 +241,17 @@ SIGNATURES = {
     "mlh_cs_fold_and_sums": (_I, [_P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P]),
     "mlh_cs_sumcheck_prove": (_I, [_P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P]),
     "mlh_cs_sumcheck_verify": (_I, [_P, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "mlh_cs_sumcheck_prove_sums": (_I, [_P, _P, _U32, _P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P]),
+    "mlh_cs_sumcheck_verify_sums": (_I, [_P, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
     "mlh_trace_columns": (_I, [_P, _P, _U32, _U32, _P]),
+    "mlh_trace_columns_range": (_I, [_P, _P, _U32, _U32, _U32, _U32, _P]),
+    "mlh_trace_columns_range_launch_info": (_I, [_U32, _U32, _U32, _U32, ctypes.POINTER(_U32),
+                                                 ctypes.POINTER(_U32)]),
+    "mlh_trace_commit_range": (_I, [_P, _P, _U32, _U32, _U32, _U32, ctypes.POINTER(_P)]),
+    "mlh_system_trace_randoms": (_I, [_P, _P, _U32, _P]),
+    "mlh_system_prove_phased": (_I, [_P, _P, _P, _P, _U32, _P, _P, _P, _P,
+                                     ctypes.POINTER(PhasedProofC)]),
+    "mlh_system_verify_phased": (_I, [_P, _U32, _U32, _U32, _P, _P, ctypes.POINTER(PhasedProofC), _P]),
     "mlh_trace_columns_launch_info": (_I, [_U32, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     "mlh_trace_commit": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(_P)]),
     "mlh_trace_commitment_root": (_I, [_P, _P]),

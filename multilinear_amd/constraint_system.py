@@ -11,6 +11,11 @@ and on the host (verifier).  ``Commitment`` is a TODO in the reference
 trace's columns (mlh_trace_commit), and ``System.committed_prover`` /
 ``System.prove`` / ``SystemProof.verify`` compose it with the sumcheck into a
 proof a verifier checks without the trace (mlh_system_prove / _verify).
+``WitnessLayout.pre_random_columns`` and ``sum_columns`` (system.rs:23-29) are
+the two-phase proof: ``System.phased_prover`` commits to the pre-random
+columns and hands out the trace randoms, the caller fills the other columns
+(``field_inv`` and the other field ops below), and ``prove`` /
+``PhasedSystemProof.verify`` are mlh_system_prove_phased / _verify_phased.
 """
 import ctypes
 import struct
@@ -265,18 +270,68 @@ class Trace:
         return _split(out, self._width)
 
 
-def trace_columns(dev_matrix, width, device=0):
+def trace_columns(dev_matrix, width, device=0, columns=None):
     """The row-major (height * width, 4) trace as its width column MLEs,
     column-major: a new tensor, column j at rows [j * height, (j + 1) * height)
-    (mlh_trace_columns)."""
+    (mlh_trace_columns).  columns = (col0, ncols): those columns only
+    (mlh_trace_columns_range)."""
     n = dev_matrix.shape[0]
     assert width >= 1 and n % width == 0
     height = n // width
     assert height & (height - 1) == 0 and height > 0
     ctx = context(device)
+    if columns is not None:
+        col0, ncols = columns
+        out = empty(height * ncols, device)
+        check(lib().mlh_trace_columns_range(ctx, ptr(dev_matrix), height.bit_length() - 1, width,
+                                            col0, ncols, ptr(out)), ctx)
+        return out
     out = empty(n, device)
     check(lib().mlh_trace_columns(ctx, ptr(dev_matrix), height.bit_length() - 1, width, ptr(out)),
           ctx)
+    return out
+
+
+# ---- field ops on device vectors (field.rs:66-118) ----------------------------
+
+def _field2(fn, a, b, out, device):
+    ctx = context(device)
+    out = empty(a.shape[0], device) if out is None else out
+    check(fn(ctx, ptr(a), ptr(b), ptr(out), a.shape[0]), ctx)
+    return out
+
+
+def field_add(a, b, out=None, device=0):
+    return _field2(lib().mlh_field_add, a, b, out, device)
+
+
+def field_sub(a, b, out=None, device=0):
+    return _field2(lib().mlh_field_sub, a, b, out, device)
+
+
+def field_mul(a, b, out=None, device=0):
+    return _field2(lib().mlh_field_mul, a, b, out, device)
+
+
+def field_neg(a, out=None, device=0):
+    ctx = context(device)
+    out = empty(a.shape[0], device) if out is None else out
+    check(lib().mlh_field_neg(ctx, ptr(a), ptr(out), a.shape[0]), ctx)
+    return out
+
+
+def field_scale(a, c, out=None, device=0):
+    ctx = context(device)
+    out = empty(a.shape[0], device) if out is None else out
+    check(lib().mlh_field_scale(ctx, ptr(a), fe_bytes(c), ptr(out), a.shape[0]), ctx)
+    return out
+
+
+def field_inv(a, out=None, device=0):
+    """out[i] = 1 / a[i], zero -> zero (mlh_field_inv); out may be a itself."""
+    ctx = context(device)
+    out = empty(a.shape[0], device) if out is None else out
+    check(lib().mlh_field_inv(ctx, ptr(a), ptr(out), a.shape[0]), ctx)
     return out
 
 
@@ -298,11 +353,18 @@ class Commitment:
             pass
 
     @staticmethod
-    def new(trace, device=0):  # trace.rs:44-47
+    def new(trace, device=0, columns=None):  # trace.rs:44-47
+        """columns = (col0, ncols): a commitment to those columns only
+        (mlh_trace_commit_range)."""
         ctx = context(device)
         h = ctypes.c_void_p()
-        check(lib().mlh_trace_commit(ctx, ptr(trace.matrix()), trace.height().bit_length() - 1,
-                                     trace.width(), ctypes.byref(h)), ctx)
+        L = trace.height().bit_length() - 1
+        if columns is not None:
+            check(lib().mlh_trace_commit_range(ctx, ptr(trace.matrix()), L, trace.width(),
+                                               columns[0], columns[1], ctypes.byref(h)), ctx)
+        else:
+            check(lib().mlh_trace_commit(ctx, ptr(trace.matrix()), L, trace.width(),
+                                         ctypes.byref(h)), ctx)
         return Commitment(h.value, device)
 
     def root(self):
@@ -351,6 +413,108 @@ class SystemProof:
                                        constraints.degree()))
         return lib().mlh_system_verify(prog.h, self.log_height, fe_bytes(total_sum),
                                        ctypes.byref(self.c), transcript.h) == 0
+
+
+def _column_mask(layout):
+    m = 0
+    for j in layout.sum_columns:
+        if not 0 <= j < layout.columns:
+            raise ValueError("sum column %r outside the trace" % (j,))
+        m |= 1 << j
+    return m
+
+
+class PhasedSystemProof:
+    """mlh_phased_proof: the sumcheck polynomials, Trace::evaluate(rs) and the
+    openings of the two commitments (columns [0, P) and [P, W)) at rs."""
+
+    def __init__(self, log_height, width, degree, pre_random_columns, sum_column_mask):
+        self.log_height, self.width, self.degree = log_height, width, degree
+        self.pre_random_columns, self.sum_column_mask = pre_random_columns, sum_column_mask
+        self._polys = (ctypes.c_uint8 * (16 * (degree + 1) * log_height))()
+        self._output = (ctypes.c_uint8 * (16 * width))()
+        P = pre_random_columns
+        self.pcs = [BatchedPCSProof(log_height, P)]
+        if P < width:
+            self.pcs.append(BatchedPCSProof(log_height, width - P))
+        self.c = _lib.PhasedProofC()
+        self.c.log_height, self.c.width, self.c.degree = log_height, width, degree
+        self.c.pre_random_columns, self.c.sum_column_mask = P, sum_column_mask
+        self.c.sumcheck_polys = ctypes.cast(self._polys, ctypes.c_void_p)
+        self.c.output = ctypes.cast(self._output, ctypes.c_void_p)
+        for i, p in enumerate(self.pcs):
+            self.c.pcs[i] = p.c
+
+    def _sync(self):  # the struct holds copies of the nested ones
+        for i, p in enumerate(self.pcs):
+            p.c = self.c.pcs[i]
+            p.fri_proof.c = self.c.pcs[i].fri
+
+    @property
+    def sumcheck_polynomials(self):
+        D = self.degree + 1
+        flat = _split(self._polys, D * self.log_height)
+        return [flat[D * k:D * k + D] for k in range(self.log_height)]
+
+    @property
+    def output(self):
+        return _split(self._output, self.width)
+
+    @property
+    def commitments(self):
+        return [bytes(self.c.pcs[i].fri.batch_commitment) for i in range(len(self.pcs))]
+
+    def verify(self, transcript, constraints, layout, total_sum, column_sum):
+        """mlh_system_verify_phased, host only: True iff accepted.  The
+        transcript is the one the prover started from; it is advanced only on
+        True."""
+        prog = Program(compile_program(constraints.constraints(), layout.columns, layout.randoms,
+                                       constraints.degree()))
+        return lib().mlh_system_verify_phased(prog.h, self.log_height, layout.pre_random_columns,
+                                              _column_mask(layout), fe_bytes(total_sum),
+                                              fe_bytes(column_sum), ctypes.byref(self.c),
+                                              transcript.h) == 0
+
+
+class PhasedProver:
+    """System::prover for a layout with pre_random_columns / sum_columns
+    (system.rs:17-30, 56-72): holds the commitment to columns [0, P) and the
+    trace randoms drawn after it; ``prove`` commits to the other columns of
+    the matrix as it then stands."""
+
+    def __init__(self, transcript, constraints, layout, trace, device=0):
+        P, W = layout.pre_random_columns, layout.columns
+        if not 1 <= P <= W or W != trace.width():
+            raise ValueError("pre_random_columns must be in 1..columns, columns the trace's width")
+        self._constraints, self._layout, self._trace, self._device = constraints, layout, trace, device
+        self._mask = _column_mask(layout)
+        self.program = Program(compile_program(constraints.constraints(), W, layout.randoms,
+                                               constraints.degree()))
+        self._com1 = Commitment.new(trace, device, columns=(0, P))
+        out = (ctypes.c_uint8 * (16 * max(layout.randoms, 1)))()
+        check(lib().mlh_system_trace_randoms(transcript.h, self._com1.root(), layout.randoms, out))
+        self.randoms = _split(out, layout.randoms)
+        self._entry = transcript.random()
+
+    def commitment(self):
+        return self._com1
+
+    def prove(self, transcript, total_sum, column_sum):
+        """mlh_system_prove_phased on a clone of the trace's matrix."""
+        if transcript.random() != self._entry:
+            raise ValueError("prove needs the transcript in the state phased_prover was given")
+        ctx = context(self._device)
+        t, lay = self._trace, self._layout
+        P, W = lay.pre_random_columns, lay.columns
+        com2 = Commitment.new(t, self._device, columns=(P, W - P)) if P < W else None
+        p = PhasedSystemProof(self._com1.log_height, W, self._constraints.degree(), P, self._mask)
+        work = t.matrix().clone()
+        check(lib().mlh_system_prove_phased(ctx, self.program.h, self._com1.h,
+                                            com2.h if com2 else None, self._mask, ptr(work),
+                                            fe_bytes(total_sum), fe_bytes(column_sum), transcript.h,
+                                            ctypes.byref(p.c)), ctx)
+        p._sync()
+        return p
 
 
 class ChallengeSet:
@@ -424,6 +588,15 @@ class System:
         s._commitment = com
         s._entry = transcript.random()
         return s
+
+    @staticmethod
+    def phased_prover(transcript, constraints, layout, trace, device=0):
+        """The two-phase prover: commits to columns [0, pre_random_columns) of
+        the trace and exposes ``.randoms``; ``transcript`` is left as it was
+        (``.prove`` absorbs).  The caller then fills the other columns of the
+        trace's matrix in place and calls ``.prove(transcript, total_sum,
+        column_sum)``."""
+        return PhasedProver(transcript, constraints, layout, trace, device)
 
     def commitment(self):
         return self._commitment

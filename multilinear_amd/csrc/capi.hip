@@ -52,6 +52,11 @@ using namespace mlh;
 // are never evicted.
 constexpr uint64_t kTablePin = 24;
 
+static bool ranges_overlap(const void* a, const void* b, uint64_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y ? y - x < bytes : x - y < bytes;
+}
+
 static mlh_status table_make_room(mlh_ctx* ctx, size_t need) {
   if (ctx->table_bytes + need <= ctx->table_limit) return MLH_OK;
   std::vector<std::pair<uint64_t, TableKey>> order;
@@ -603,6 +608,18 @@ mlh_status mlh_field_scale(mlh_ctx* ctx, const void* a, const uint8_t c[16], voi
   if (h_load(c) >= kModulus) return fail(ctx, MLH_ERR_INVALID, "scalar not canonical");
   HIP_TRY(ctx, launch_vec_op(4, reinterpret_cast<const fe*>(a), nullptr, reinterpret_cast<fe*>(out),
                              n, ctx->stream, to_fe(h_load(c))));
+  return MLH_OK;
+}
+mlh_status mlh_field_inv(mlh_ctx* ctx, const void* a, void* out, uint64_t n) {
+  if (!ctx) return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (n == 0) return MLH_OK;
+  if (!a || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (a != out && ranges_overlap(a, out, n * 16))
+    return fail(ctx, MLH_ERR_INVALID, "mlh_field_inv: in place or disjoint buffers only");
+  ProfScope ps(ctx, "field_inv");
+  HIP_TRY(ctx, launch_field_inv(reinterpret_cast<const fe*>(a), reinterpret_cast<fe*>(out), n,
+                                ctx->stream));
+  ps.end();
   return MLH_OK;
 }
 
@@ -2585,11 +2602,6 @@ struct mlh_trace_commitment {
   }
 };
 
-static bool ranges_overlap(const void* a, const void* b, uint64_t bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y ? y - x < bytes : x - y < bytes;
-}
-
 extern "C" {
 
 mlh_status mlh_trace_columns(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
@@ -2615,29 +2627,82 @@ mlh_status mlh_trace_columns_launch_info(uint32_t log_height, uint32_t width, ui
   return MLH_OK;
 }
 
+mlh_status mlh_trace_columns_range(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                   uint32_t width, uint32_t col0, uint32_t ncols, void* dev_out) {
+  if (!ctx || !dev_matrix || !dev_out) return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (width < 1 || width > kCsMaxWidth || log_height > kCsMaxLogHeight)
+    return fail(ctx, MLH_ERR_INVALID, "width 1..32, log_height 0..32");
+  if (ncols < 1 || col0 >= width || ncols > width - col0)
+    return fail(ctx, MLH_ERR_INVALID, "column range outside the trace");
+  // dev_out holds ncols columns; the trace is read over its whole extent
+  const uint64_t tb = ((uint64_t)width << log_height) * 16, ob = ((uint64_t)ncols << log_height) * 16;
+  const uintptr_t x = (uintptr_t)dev_matrix, y = (uintptr_t)dev_out;
+  if (x < y ? y - x < tb : x - y < ob)
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_columns_range is out of place: the buffers overlap");
+  ProfScope ps(ctx, "trace_columns_range");
+  HIP_TRY(ctx, launch_trace_columns_range(reinterpret_cast<const fe*>(dev_matrix),
+                                          reinterpret_cast<fe*>(dev_out), log_height, width, col0,
+                                          ncols, ctx->stream));
+  ps.end();
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_columns_range_launch_info(uint32_t log_height, uint32_t width, uint32_t col0,
+                                               uint32_t ncols, uint32_t* tile_rows,
+                                               uint32_t* blocks) {
+  if (!tile_rows || !blocks || width < 1 || width > kCsMaxWidth || log_height > kCsMaxLogHeight ||
+      ncols < 1 || col0 >= width || ncols > width - col0)
+    return MLH_ERR_INVALID;
+  *tile_rows = tc_tile_rows(ncols);
+  *blocks = tc_blocks(1ull << log_height, ncols);
+  return MLH_OK;
+}
+
+// Commitment::new over columns [col0, col0 + ncols); full = mlh_trace_commit's
+// own path (mlh_trace_columns, one contiguous tile per block).
+static mlh_status trace_commit_impl(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                    uint32_t width, uint32_t col0, uint32_t ncols, bool full,
+                                    mlh_trace_commitment** out) {
+  std::unique_ptr<mlh_trace_commitment> c(new mlh_trace_commitment());
+  c->ctx = ctx;
+  c->log_height = log_height;
+  c->width = ncols;
+  const uint64_t n = 1ull << log_height;
+  MLH_TRY(pool_alloc(ctx, ncols * n * 16, &c->evals));
+  MLH_TRY(pool_alloc(ctx, ncols * n * 32, &c->codes));
+  MLH_TRY(pool_alloc(ctx, mlh_merkle_layers_bytes(n), &c->tree));
+  if (full)
+    MLH_TRY(mlh_trace_columns(ctx, dev_matrix, log_height, width, c->evals));
+  else
+    MLH_TRY(mlh_trace_columns_range(ctx, dev_matrix, log_height, width, col0, ncols, c->evals));
+  fe* codes = reinterpret_cast<fe*>(c->codes);
+  MLH_TRY(batched_pcs_codes(ctx, c->evals, ncols, log_height, codes));
+  // the batch layer of BatchedFriProverData::init (batched_fri.rs:41-81)
+  uint8_t* bt = reinterpret_cast<uint8_t*>(c->tree);
+  HIP_TRY(ctx, launch_batch_pairs_leaves(codes, ncols, 2 * n, bt, ctx->stream));
+  HIP_TRY(ctx, launch_merkle_levels(bt, n, ctx->stream));
+  MLH_TRY(read_root(ctx, bt, n, c->root));
+  *out = c.release();
+  return MLH_OK;
+}
+
 mlh_status mlh_trace_commit(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
                             uint32_t width, mlh_trace_commitment** out) {
   if (!ctx || !dev_matrix || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
   if (width < 1 || width > kCsMaxWidth || log_height < 1 || log_height > kCsMaxLogHeight)
     return fail(ctx, MLH_ERR_INVALID, "width 1..32, log_height 1..32");
-  std::unique_ptr<mlh_trace_commitment> c(new mlh_trace_commitment());
-  c->ctx = ctx;
-  c->log_height = log_height;
-  c->width = width;
-  const uint64_t n = 1ull << log_height;
-  MLH_TRY(pool_alloc(ctx, width * n * 16, &c->evals));
-  MLH_TRY(pool_alloc(ctx, width * n * 32, &c->codes));
-  MLH_TRY(pool_alloc(ctx, mlh_merkle_layers_bytes(n), &c->tree));
-  MLH_TRY(mlh_trace_columns(ctx, dev_matrix, log_height, width, c->evals));
-  fe* codes = reinterpret_cast<fe*>(c->codes);
-  MLH_TRY(batched_pcs_codes(ctx, c->evals, width, log_height, codes));
-  // the batch layer of BatchedFriProverData::init (batched_fri.rs:41-81)
-  uint8_t* bt = reinterpret_cast<uint8_t*>(c->tree);
-  HIP_TRY(ctx, launch_batch_pairs_leaves(codes, width, 2 * n, bt, ctx->stream));
-  HIP_TRY(ctx, launch_merkle_levels(bt, n, ctx->stream));
-  MLH_TRY(read_root(ctx, bt, n, c->root));
-  *out = c.release();
-  return MLH_OK;
+  return trace_commit_impl(ctx, dev_matrix, log_height, width, 0, width, true, out);
+}
+
+mlh_status mlh_trace_commit_range(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                  uint32_t width, uint32_t col0, uint32_t ncols,
+                                  mlh_trace_commitment** out) {
+  if (!ctx || !dev_matrix || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (width < 1 || width > kCsMaxWidth || log_height < 1 || log_height > kCsMaxLogHeight)
+    return fail(ctx, MLH_ERR_INVALID, "width 1..32, log_height 1..32");
+  if (ncols < 1 || col0 >= width || ncols > width - col0)
+    return fail(ctx, MLH_ERR_INVALID, "column range outside the trace");
+  return trace_commit_impl(ctx, dev_matrix, log_height, width, col0, ncols, false, out);
 }
 
 mlh_status mlh_trace_commitment_root(const mlh_trace_commitment* c, uint8_t out[32]) {
@@ -2920,26 +2985,42 @@ mlh_status mlh_cs_sumcheck_prove(mlh_ctx* ctx, const mlh_cs_program* prog, uint3
                                  const uint8_t* host_randoms, const uint8_t* host_mask,
                                  const uint8_t sum[16], mlh_transcript* tr, uint8_t* polys_out,
                                  uint8_t* rs_out) {
-  if (!ctx || !sum || !tr || !cs_args_ok(prog, width, dev_matrix, dev_delta, host_randoms, host_mask) ||
-      log_height > kCsMaxLogHeight || h_load(sum) >= kModulus)
+  return mlh_cs_sumcheck_prove_sums(ctx, prog, width, dev_matrix, dev_delta, log_height, host_randoms,
+                                    host_mask, 0, nullptr, sum, tr, polys_out, rs_out);
+}
+
+mlh_status mlh_cs_sumcheck_prove_sums(mlh_ctx* ctx, const mlh_cs_program* prog, uint32_t width,
+                                      void* dev_matrix, void* dev_delta, uint32_t log_height,
+                                      const uint8_t* host_randoms, const uint8_t* host_mask,
+                                      uint32_t sum_column_mask, const uint8_t* beta,
+                                      const uint8_t claim[16], mlh_transcript* tr,
+                                      uint8_t* polys_out, uint8_t* rs_out) {
+  if (!ctx || !claim || !tr || !cs_args_ok(prog, width, dev_matrix, dev_delta, host_randoms, host_mask) ||
+      log_height > kCsMaxLogHeight || h_load(claim) >= kModulus)
     return fail(ctx, MLH_ERR_INVALID, "bad argument");
+  const uint32_t smask = sum_column_mask;
+  if (smask && (!beta || h_load(beta) >= kModulus || (width < 32 && (smask >> width))))
+    return fail(ctx, MLH_ERR_INVALID, "sum columns: beta missing or a mask bit at or above the width");
   const uint32_t L = log_height;
   if (L == 0) return MLH_OK;  // zero rounds (sumcheck.rs:160-161)
   CsCall cc(ctx);
   MLH_TRY(cc.init(ctx, prog, host_randoms, host_mask));
   const uint32_t D = cc.dev.D;
-  // [DevSha | claim | polys 16 D x L | rs 16 x L]; one sync, at the end
+  // [DevSha | claim | polys 16 D x L | rs 16 x L | sum columns: 2 x kCsMaxBlocks partials]; one
+  // sync, at the end
   const uint64_t out_bytes = 16ull * (D + 1) * L;
   PoolBuf sc(ctx);
-  MLH_TRY(sc.alloc(144 + out_bytes));
+  MLH_TRY(sc.alloc(144 + out_bytes + (smask ? 32ull * kCsMaxBlocks : 0)));
   uint8_t* sb = sc.as<uint8_t>();
   DevSha* dt = reinterpret_cast<DevSha*>(sb);
   fe* prev = reinterpret_cast<fe*>(sb + 128);
   fe* polys = reinterpret_cast<fe*>(sb + 144);
   fe* rs = polys + (uint64_t)D * L;
+  fe* lin = smask ? rs + L : nullptr;
+  const fe fbeta = smask ? to_fe(h_load(beta)) : fe{};
   static_assert(sizeof(DevSha) <= 128, "DevSha slot");
   memcpy(ctx->pinned, &tr->sha, sizeof(DevSha));
-  memcpy(ctx->pinned + 128, sum, 16);
+  memcpy(ctx->pinned + 128, claim, 16);
   HIP_TRY(ctx, hipMemcpyAsync(sb, ctx->pinned, 144, hipMemcpyHostToDevice, ctx->stream));
   fe* m = reinterpret_cast<fe*>(dev_matrix);
   fe* d = reinterpret_cast<fe*>(dev_delta);
@@ -2947,21 +3028,21 @@ mlh_status mlh_cs_sumcheck_prove(mlh_ctx* ctx, const mlh_cs_program* prog, uint3
   {
     ProfScope ps(ctx, "cs_sums");
     HIP_TRY(ctx, launch_cs_sums(cc.dev, cc.threads, m, d, 1ull << (L - 1), ctx->partials,
-                                ctx->stream, &nb));
+                                ctx->stream, &nb, smask, lin));
     ps.end();
   }
   for (uint32_t k = 0; k < L; ++k) {
     {
       ProfScope ps(ctx, "cs_round");
       HIP_TRY(ctx, launch_cs_round(ctx->partials, nb, D, cc.vinv, prev, dt, polys + (uint64_t)D * k,
-                                   rs + k, ctx->stream));
+                                   rs + k, ctx->stream, lin, fbeta));
       ps.end();
     }
     const uint64_t S = 1ull << (L - k);
     if (S >= 4) {  // fold with r_k + round k+1's sums, one pass
       ProfScope ps(ctx, "cs_fold_sums");
       HIP_TRY(ctx, launch_cs_fold_sums(cc.dev, cc.threads, m, d, S, fe{}, rs + k, ctx->partials,
-                                       ctx->stream, &nb));
+                                       ctx->stream, &nb, smask, lin));
       ps.end();
     } else {
       ProfScope ps(ctx, "cs_fold");
@@ -3057,6 +3138,93 @@ mlh_status mlh_system_prove(mlh_ctx* ctx, const mlh_cs_program* prog,
   proof->log_height = L;
   proof->width = W;
   proof->degree = P.degree;
+  guard.keep();
+  return MLH_OK;
+}
+
+// The two-phase proof (WitnessLayout::pre_random_columns / sum_columns,
+// system.rs:17-30): mlhip.h gives the transcript order.
+mlh_status mlh_system_prove_phased(mlh_ctx* ctx, const mlh_cs_program* prog,
+                                   const mlh_trace_commitment* com1,
+                                   const mlh_trace_commitment* com2, uint32_t sum_column_mask,
+                                   void* dev_matrix, const uint8_t sum[16],
+                                   const uint8_t column_sum[16], mlh_transcript* tr,
+                                   mlh_phased_proof* proof) {
+  if (!ctx || !prog || !com1 || !dev_matrix || !sum || !column_sum || !tr || !proof ||
+      !proof->sumcheck_polys || !proof->output)
+    return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (com1->ctx != ctx || (com2 && com2->ctx != ctx))
+    return fail(ctx, MLH_ERR_INVALID, "commitment of another context");
+  const CsProgram& P = prog->p;
+  const uint32_t L = com1->log_height, W = P.width, P1 = com1->width, P2 = com2 ? com2->width : 0;
+  if (P1 < 1 || P1 + P2 != W || (com2 && com2->log_height != L))
+    return fail(ctx, MLH_ERR_INVALID,
+                "the commitments' widths must add up to the program's (com2 null iff all columns "
+                "are pre-random), over the same rows");
+  if (W < 32 && (sum_column_mask >> W))
+    return fail(ctx, MLH_ERR_INVALID, "sum column at or above the width");
+  if (h_load(sum) >= kModulus || h_load(column_sum) >= kModulus)
+    return fail(ctx, MLH_ERR_INVALID, "non-canonical sum");
+  TranscriptGuard guard(tr);
+  // 1. root 1; 2. the trace randoms (ChallengeSet::new's trace, system.rs:139); 3. root 2;
+  // 4. the row and constraint challenges and the mask
+  mlh_transcript_absorb(tr, com1->root, 32);
+  uint32_t log_nc = 0;
+  while ((1ull << log_nc) < P.n_constraints) ++log_nc;
+  std::vector<uint8_t> row(16ull * L), rnd(16ull * P.n_randoms + 16), cons(16ull * log_nc + 16),
+      mask(16ull * P.n_constraints), rs(16ull * L);
+  {
+    uint8_t c[16];
+    mlh_transcript_next_challenge(tr, c);
+    for (uint32_t i = 0; i < P.n_randoms; ++i) memcpy(rnd.data() + 16ull * i, c, 16);
+  }
+  if (com2) mlh_transcript_absorb(tr, com2->root, 32);
+  if (mlh_system_challenges(tr, L, 0, P.n_constraints, row.data(), nullptr, cons.data(),
+                            mask.data()) != MLH_OK)
+    return fail(ctx, MLH_ERR_INVALID, "challenge set");
+  // 5. beta after the claimed column sum; the combined claim
+  uint8_t beta[16] = {0}, claim[16];
+  memcpy(claim, sum, 16);
+  if (sum_column_mask) {
+    mlh_transcript_absorb(tr, column_sum, 16);
+    mlh_transcript_next_challenge(tr, beta);
+    h_store(claim, h_add(h_load(sum), h_mul(h_load(beta), h_load(column_sum))));
+  }
+  // 6. the sumcheck; output = row 0 of the folded matrix
+  PoolBuf delta(ctx);
+  MLH_TRY(delta.alloc(16ull << L));
+  MLH_TRY(mlh_eq_table(ctx, row.data(), L, delta.p));
+  {
+    ProfScope ps(ctx, "system_sumcheck");
+    MLH_TRY(mlh_cs_sumcheck_prove_sums(ctx, prog, W, dev_matrix, delta.p, L, rnd.data(), mask.data(),
+                                       sum_column_mask, beta, claim, tr, proof->sumcheck_polys,
+                                       rs.data()));
+    ps.end();
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev_matrix, 16ull * W, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<uint8_t> output(ctx->pinned, ctx->pinned + 16ull * W);
+  // 7., 8. the openings, each on its handle's codes, evaluations and batch tree
+  {
+    ProfScope ps(ctx, "system_open");
+    MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com1->codes), com1->evals,
+                             reinterpret_cast<const uint8_t*>(com1->tree), P1, L, rs.data(),
+                             output.data(), tr, &proof->pcs[0]));
+    ps.end();
+  }
+  if (com2) {
+    ProfScope ps(ctx, "system_open2");
+    MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com2->codes), com2->evals,
+                             reinterpret_cast<const uint8_t*>(com2->tree), P2, L, rs.data(),
+                             output.data() + 16ull * P1, tr, &proof->pcs[1]));
+    ps.end();
+  }
+  memcpy(proof->output, output.data(), output.size());
+  proof->log_height = L;
+  proof->width = W;
+  proof->degree = P.degree;
+  proof->pre_random_columns = P1;
+  proof->sum_column_mask = sum_column_mask;
   guard.keep();
   return MLH_OK;
 }

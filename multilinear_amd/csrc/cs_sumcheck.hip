@@ -24,6 +24,15 @@
 // a height-4q table: it folds them with r, writes the folded half back in
 // place (each element is read and written by one thread only) and leaves the
 // folded pair (new[i], new[i + q]) in LDS for the next round's sums.
+//
+// Sum columns (template flag SUMS; the claim sum_i [delta_i composition(row_i)
+// + beta sum_{j in S} row_i[j]]): the linear part of the round polynomial at
+// X = t is A + (t - 1) B with A = sum_rows sum_{j in S} hi and B = sum_rows
+// sum_{j in S} (hi - lo), both read from the slots the chunk's loads filled
+// (values at X = 1 and steps) before the interpreter advances them.  A lane
+// keeps its A and B in registers; the block reduces them into lin[block] and
+// lin[gridDim.x + block], and cs_round_lin_kernel adds beta (A + (t - 1) B)
+// to evals[t].  SUMS = false is the code without any of it.
 #include "bfly_asm.hpp"
 #include "cs_program.hpp"
 #include "cs_sumcheck.hpp"
@@ -97,24 +106,39 @@ __device__ __forceinline__ void cs_accumulate(const CsDev& P, fe* lane_lds, uint
   }
 }
 
+// This lane's row of the sum columns (smask: bit j = column j), before
+// cs_accumulate advances the slots: la += sum hi, lb += sum (hi - lo).
+__device__ __forceinline__ void cs_linear(const CsDev& P, const fe* lane_lds, uint32_t B,
+                                          uint32_t smask, fe& la, fe& lb) {
+  const uint32_t step0 = P.width + P.n_temps;
+  for (uint32_t j = 0; j < P.width; ++j)
+    if ((smask >> j) & 1u) {
+      la = fe_add(la, lane_lds[j * B]);
+      lb = fe_add(lb, lane_lds[(step0 + j) * B]);
+    }
+}
+
+// *dst = the block's sum of v (red: 4 elements of LDS)
+__device__ __forceinline__ void cs_block_sum(fe v, uint32_t B, fe* red, fe* __restrict__ dst) {
+  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = fe_add(v, shfl_xor_fe(v, m));
+  if (lane == 0) red[wid] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (uint32_t w = 1; w < (B >> 6); ++w) v = fe_add(v, red[w]);
+    fe_store(dst, v);
+  }
+  __syncthreads();
+}
+
 // partials[t * gridDim.x + blockIdx.x] = the block's sum t
 __device__ __forceinline__ void cs_block_sums(const CsDev& P, const fe* lane_lds, uint32_t B,
                                               fe* __restrict__ partials) {
   __shared__ fe red[4];
   const uint32_t acc0 = 2 * P.width + P.n_temps;
-  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  for (uint32_t t = 0; t < P.D; ++t) {
-    fe v = lane_lds[(acc0 + t) * B];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fe_add(v, shfl_xor_fe(v, m));
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      for (uint32_t w = 1; w < (B >> 6); ++w) v = fe_add(v, red[w]);
-      fe_store(partials + (uint64_t)t * gridDim.x + blockIdx.x, v);
-    }
-    __syncthreads();
-  }
+  for (uint32_t t = 0; t < P.D; ++t)
+    cs_block_sum(lane_lds[(acc0 + t) * B], B, red, partials + (uint64_t)t * gridDim.x + blockIdx.x);
 }
 
 __device__ __forceinline__ void cs_zero_sums(const CsDev& P, fe* lane_lds, uint32_t B) {
@@ -122,12 +146,15 @@ __device__ __forceinline__ void cs_zero_sums(const CsDev& P, fe* lane_lds, uint3
   for (uint32_t t = 0; t < P.D; ++t) lane_lds[(acc0 + t) * B] = fe_zero();
 }
 
-__global__ void __launch_bounds__(256)
-cs_sums_kernel(const CsDev P, const fe* __restrict__ m, const fe* __restrict__ d, uint64_t h,
-               fe* __restrict__ partials) {
+template <bool SUMS>
+__device__ __forceinline__ void cs_sums_body(const CsDev& P, const fe* __restrict__ m,
+                                             const fe* __restrict__ d, uint64_t h,
+                                             fe* __restrict__ partials, uint32_t smask,
+                                             fe* __restrict__ lin) {
   extern __shared__ fe cs_lds[];
   const uint32_t B = blockDim.x, tid = threadIdx.x, W = P.width, step0 = W + P.n_temps;
   fe* lane_lds = cs_lds + tid;
+  fe la = fe_zero(), lb = fe_zero();
   cs_zero_sums(P, lane_lds, B);
   for (uint64_t base = (uint64_t)blockIdx.x * B; base < h; base += (uint64_t)gridDim.x * B) {
     const uint32_t nrows = h - base < B ? (uint32_t)(h - base) : B;
@@ -146,21 +173,42 @@ cs_sums_kernel(const CsDev P, const fe* __restrict__ m, const fe* __restrict__ d
       dd = fe_sub(dc, fe_load(d + base + tid));
     }
     __syncthreads();
+    if (SUMS && valid) cs_linear(P, lane_lds, B, smask, la, lb);
     cs_accumulate(P, lane_lds, B, valid, dc, dd);
     __syncthreads();  // the next chunk's loads overwrite other lanes' slots
   }
   cs_block_sums(P, lane_lds, B, partials);
+  if (SUMS) {
+    __shared__ fe lred[4];
+    cs_block_sum(la, B, lred, lin + blockIdx.x);
+    cs_block_sum(lb, B, lred, lin + gridDim.x + blockIdx.x);
+  }
 }
 
+// (the kernels without sum columns keep their argument lists)
 __global__ void __launch_bounds__(256)
-cs_fold_sums_kernel(const CsDev P, fe* m, fe* d, uint64_t S, fe r, const fe* __restrict__ rp,
-                    fe* __restrict__ partials) {
+cs_sums_kernel(const CsDev P, const fe* __restrict__ m, const fe* __restrict__ d, uint64_t h,
+               fe* __restrict__ partials) {
+  cs_sums_body<false>(P, m, d, h, partials, 0u, nullptr);
+}
+__global__ void __launch_bounds__(256)
+cs_sums_lin_kernel(const CsDev P, const fe* __restrict__ m, const fe* __restrict__ d, uint64_t h,
+                   fe* __restrict__ partials, uint32_t smask, fe* __restrict__ lin) {
+  cs_sums_body<true>(P, m, d, h, partials, smask, lin);
+}
+
+template <bool SUMS>
+__device__ __forceinline__ void cs_fold_sums_body(const CsDev& P, fe* m, fe* d, uint64_t S, fe r,
+                                                  const fe* __restrict__ rp,
+                                                  fe* __restrict__ partials, uint32_t smask,
+                                                  fe* __restrict__ lin) {
   extern __shared__ fe cs_lds[];
   if (rp) r = fe_load(rp);
   r = fe_vgpr(r);
   const uint32_t B = blockDim.x, tid = threadIdx.x, W = P.width, step0 = W + P.n_temps;
   const uint64_t q = S / 4, qW = q * W;
   fe* lane_lds = cs_lds + tid;
+  fe la = fe_zero(), lb = fe_zero();
   cs_zero_sums(P, lane_lds, B);
   for (uint64_t base = (uint64_t)blockIdx.x * B; base < q; base += (uint64_t)gridDim.x * B) {
     const uint32_t nrows = q - base < B ? (uint32_t)(q - base) : B;
@@ -187,10 +235,27 @@ cs_fold_sums_kernel(const CsDev P, fe* m, fe* d, uint64_t S, fe r, const fe* __r
       dd = fe_sub(n1, n0);
     }
     __syncthreads();
+    if (SUMS && valid) cs_linear(P, lane_lds, B, smask, la, lb);
     cs_accumulate(P, lane_lds, B, valid, dc, dd);
     __syncthreads();
   }
   cs_block_sums(P, lane_lds, B, partials);
+  if (SUMS) {
+    __shared__ fe lred[4];
+    cs_block_sum(la, B, lred, lin + blockIdx.x);
+    cs_block_sum(lb, B, lred, lin + gridDim.x + blockIdx.x);
+  }
+}
+
+__global__ void __launch_bounds__(256)
+cs_fold_sums_kernel(const CsDev P, fe* m, fe* d, uint64_t S, fe r, const fe* __restrict__ rp,
+                    fe* __restrict__ partials) {
+  cs_fold_sums_body<false>(P, m, d, S, r, rp, partials, 0u, nullptr);
+}
+__global__ void __launch_bounds__(256)
+cs_fold_sums_lin_kernel(const CsDev P, fe* m, fe* d, uint64_t S, fe r, const fe* __restrict__ rp,
+                        fe* __restrict__ partials, uint32_t smask, fe* __restrict__ lin) {
+  cs_fold_sums_body<true>(P, m, d, S, r, rp, partials, smask, lin);
 }
 
 // SumcheckTables::fold (sumcheck.rs:234-247): elements [0, hW) of the matrix
@@ -246,7 +311,9 @@ __device__ __forceinline__ void cs_update_bytes(DevSha& s, const uint8_t* p, uin
     if (s.len % 64 == 0) dsha_compress_buf(s);
   }
 }
-__device__ inline fe cs_challenge(const DevSha& s0, DevSha& c, uint8_t* pad) {
+// (forced inline: with two round kernels it has two call sites, and a call
+// left out of line costs each of them a stack frame)
+__device__ __forceinline__ fe cs_challenge(const DevSha& s0, DevSha& c, uint8_t* pad) {
   const uint64_t bits = s0.len * 8;
   const uint32_t fill = (uint32_t)(s0.len % 64);
   uint32_t h[8];
@@ -293,10 +360,13 @@ __device__ inline fe cs_challenge(const DevSha& s0, DevSha& c, uint8_t* pad) {
 // coefficients as vinv * evals (lane k: coefficient k; the exact interpolation
 // of polynomials.rs:51-87), absorb LE16(c1) .. LE16(cD) (:194-197), r =
 // next_challenge(), claim = pol(r) by Horner (polynomials.rs:9-14).
-__global__ void __launch_bounds__(kRedThreads)
-cs_round_kernel(const fe* __restrict__ partials, uint32_t nb, uint32_t D,
-                const fe* __restrict__ vinv, fe* prev, DevSha* t, fe* __restrict__ poly_out,
-                fe* __restrict__ r_out) {
+// SUMS: evals[t] += beta (A + (t - 1) B), A and B reduced from lin (the sum
+// columns' linear part; the header comment).
+template <bool SUMS>
+__device__ __forceinline__ void cs_round_body(const fe* __restrict__ partials, uint32_t nb, uint32_t D,
+                                              const fe* __restrict__ vinv, fe* prev, DevSha* t,
+                                              fe* __restrict__ poly_out, fe* __restrict__ r_out,
+                                              const fe* __restrict__ lin, const fe& beta) {
   __shared__ DevSha s, sc;
   __shared__ uint32_t stage[4];
   __shared__ uint8_t pad[72];
@@ -304,6 +374,16 @@ cs_round_kernel(const fe* __restrict__ partials, uint32_t nb, uint32_t D,
   if (threadIdx.x < sizeof(DevSha) / 4)
     reinterpret_cast<uint32_t*>(&s)[threadIdx.x] = reinterpret_cast<const uint32_t*>(t)[threadIdx.x];
   cs_reduce_partials(partials, nb, D, ev);  // (its barriers also publish the staged state)
+  if (SUMS) {
+    __shared__ fe lv[3];  // lv[1] = A, lv[2] = B
+    cs_reduce_partials(lin, nb, 2, lv);
+    if (threadIdx.x >= 1 && threadIdx.x <= D) {
+      fe l = lv[1];
+      for (uint32_t i = 1; i < threadIdx.x; ++i) l = fe_add(l, lv[2]);
+      ev[threadIdx.x] = fe_add(ev[threadIdx.x], fe_mul(fe_vgpr(beta), l));
+    }
+    __syncthreads();
+  }
   const uint32_t N = D + 1;
   const fe claim = fe_load(prev);
   if (threadIdx.x < N) {
@@ -332,6 +412,18 @@ cs_round_kernel(const fe* __restrict__ partials, uint32_t nb, uint32_t D,
   fe_store(prev, p);
   *t = s;
 }
+__global__ void __launch_bounds__(kRedThreads)
+cs_round_kernel(const fe* __restrict__ partials, uint32_t nb, uint32_t D,
+                const fe* __restrict__ vinv, fe* prev, DevSha* t, fe* __restrict__ poly_out,
+                fe* __restrict__ r_out) {
+  cs_round_body<false>(partials, nb, D, vinv, prev, t, poly_out, r_out, nullptr, fe_zero());
+}
+__global__ void __launch_bounds__(kRedThreads)
+cs_round_lin_kernel(const fe* __restrict__ partials, uint32_t nb, uint32_t D,
+                    const fe* __restrict__ vinv, fe* prev, DevSha* t, fe* __restrict__ poly_out,
+                    fe* __restrict__ r_out, const fe* __restrict__ lin, fe beta) {
+  cs_round_body<true>(partials, nb, D, vinv, prev, t, poly_out, r_out, lin, beta);
+}
 
 // ---- launchers -------------------------------------------------------------
 
@@ -340,24 +432,35 @@ static inline size_t cs_lds_bytes(const CsDev& P, uint32_t threads) {
 }
 
 hipError_t launch_cs_sums(const CsDev& P, uint32_t threads, const fe* m, const fe* d, uint64_t h,
-                          fe* partials, hipStream_t st, uint32_t* nb) {
+                          fe* partials, hipStream_t st, uint32_t* nb, uint32_t smask, fe* lin) {
   const size_t lds = cs_lds_bytes(P, threads);
-  if (threads < 64 || threads > 256 || (threads & 63) || lds > kCsLdsBytes || P.D > kCsMaxD || h == 0)
+  if (threads < 64 || threads > 256 || (threads & 63) || lds > kCsLdsBytes || P.D > kCsMaxD || h == 0 ||
+      (smask && !lin))
     return hipErrorInvalidValue;
   const uint32_t n = cs_blocks(h, threads);
-  hipLaunchKernelGGL(cs_sums_kernel, dim3(n), dim3(threads), lds, st, P, m, d, h, partials);
+  if (smask)
+    hipLaunchKernelGGL(cs_sums_lin_kernel, dim3(n), dim3(threads), lds, st, P, m, d, h, partials,
+                       smask, lin);
+  else
+    hipLaunchKernelGGL(cs_sums_kernel, dim3(n), dim3(threads), lds, st, P, m, d, h, partials);
   *nb = n;
   return hipGetLastError();
 }
 
 hipError_t launch_cs_fold_sums(const CsDev& P, uint32_t threads, fe* m, fe* d, uint64_t S, fe r,
-                               const fe* r_dev, fe* partials, hipStream_t st, uint32_t* nb) {
+                               const fe* r_dev, fe* partials, hipStream_t st, uint32_t* nb,
+                               uint32_t smask, fe* lin) {
   const size_t lds = cs_lds_bytes(P, threads);
-  if (threads < 64 || threads > 256 || (threads & 63) || lds > kCsLdsBytes || P.D > kCsMaxD || S < 4)
+  if (threads < 64 || threads > 256 || (threads & 63) || lds > kCsLdsBytes || P.D > kCsMaxD || S < 4 ||
+      (smask && !lin))
     return hipErrorInvalidValue;
   const uint32_t n = cs_blocks(S / 4, threads);
-  hipLaunchKernelGGL(cs_fold_sums_kernel, dim3(n), dim3(threads), lds, st, P, m, d, S, r, r_dev,
-                     partials);
+  if (smask)
+    hipLaunchKernelGGL(cs_fold_sums_lin_kernel, dim3(n), dim3(threads), lds, st, P, m, d, S, r, r_dev,
+                       partials, smask, lin);
+  else
+    hipLaunchKernelGGL(cs_fold_sums_kernel, dim3(n), dim3(threads), lds, st, P, m, d, S, r, r_dev,
+                       partials);
   *nb = n;
   return hipGetLastError();
 }
@@ -372,10 +475,15 @@ hipError_t launch_cs_fold(uint32_t width, fe* m, fe* d, uint64_t S, fe r, const 
 }
 
 hipError_t launch_cs_round(const fe* partials, uint32_t nb, uint32_t D, const fe* vinv, fe* prev,
-                           DevSha* t, fe* poly_out, fe* r_out, hipStream_t st) {
+                           DevSha* t, fe* poly_out, fe* r_out, hipStream_t st, const fe* lin,
+                           fe beta) {
   if (D < 2 || D > kCsMaxD) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(cs_round_kernel, dim3(1), dim3(kRedThreads), 0, st, partials, nb, D, vinv, prev,
-                     t, poly_out, r_out);
+  if (lin)
+    hipLaunchKernelGGL(cs_round_lin_kernel, dim3(1), dim3(kRedThreads), 0, st, partials, nb, D, vinv,
+                       prev, t, poly_out, r_out, lin, beta);
+  else
+    hipLaunchKernelGGL(cs_round_kernel, dim3(1), dim3(kRedThreads), 0, st, partials, nb, D, vinv, prev,
+                       t, poly_out, r_out);
   return hipGetLastError();
 }
 

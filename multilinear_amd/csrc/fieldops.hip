@@ -37,4 +37,84 @@ hipError_t launch_vec_op(int op, const fe* a, const fe* b, fe* out, uint64_t n, 
   return hipGetLastError();
 }
 
+// ---- inverse (field.rs:113-118: Div through winter-math's inv, zero -> zero) ----
+// x^(M - 2), M - 2 = 2^128 - 45 * 2^40 - 1 = [80 ones] 1101 0010 [40 ones] in
+// binary.  With x_k = x^(2^k - 1): x_2, x_4, x_5, x_10, x_20, x_40, x_80 by
+// x_(a+b) = x_a^(2^b) * x_b (79 squarings, 7 products), then the windows 11, 0,
+// 1 (4 squarings, 2 products), 0010 (4 squarings, 1 product) and the 40 ones
+// (40 squarings, 1 product): 127 squarings + 11 products = 138, against 127 +
+// 121 for square-and-multiply.
+__device__ __forceinline__ fe fe_sqr_n(fe x, uint32_t n) {
+#pragma unroll 1
+  for (uint32_t i = 0; i < n; ++i) x = fe_sqr(x);
+  return x;
+}
+__device__ __forceinline__ fe fe_inv_chain(const fe& x) {
+  const fe x2 = fe_mul(fe_sqr(x), x);
+  const fe x4 = fe_mul(fe_sqr_n(x2, 2), x2);
+  const fe x5 = fe_mul(fe_sqr(x4), x);
+  const fe x10 = fe_mul(fe_sqr_n(x5, 5), x5);
+  const fe x20 = fe_mul(fe_sqr_n(x10, 10), x10);
+  const fe x40 = fe_mul(fe_sqr_n(x20, 20), x20);
+  fe r = fe_mul(fe_sqr_n(x40, 40), x40);  // x_80
+  r = fe_mul(fe_sqr_n(r, 2), x2);         // .. 11
+  r = fe_mul(fe_sqr_n(r, 2), x);          // .. 01
+  r = fe_sqr(fe_mul(fe_sqr_n(r, 3), x));  // .. 0010
+  return fe_mul(fe_sqr_n(r, 40), x40);    // .. 40 ones
+}
+
+__device__ __forceinline__ bool fe_is_zero(const fe& a) {
+  return (a.w[0] | a.w[1] | a.w[2] | a.w[3]) == 0u;
+}
+
+// Montgomery's trick per thread: a thread takes the kInvK elements base + k *
+// kInvThreads of its block's chunk (consecutive lanes, consecutive elements),
+// keeps the prefix products p_k = a'_0 .. a'_k in registers (a' = a with zeros
+// replaced by one), raises p_(K-1) to M - 2 once, and walks back: out_k = inv *
+// p_(k-1), inv *= a'_k, with a_k read a second time (the kernel is bound by
+// the multiplier, and holding the inputs as well would double the registers).
+// 3 products per element + 138 / kInvK.  An element is read and written by one
+// thread only and a_k is loaded before out_k is stored, so out == a is allowed.
+__global__ void __launch_bounds__(kInvThreads)
+field_inv_kernel(const fe* a, fe* out, uint64_t n, uint64_t chunks) {
+  constexpr uint32_t K = kInvK;
+  for (uint64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+    const uint64_t base = c * (uint64_t)(kInvThreads * K) + threadIdx.x;
+    if (base >= n) continue;
+    fe p[K];
+#pragma unroll
+    for (uint32_t k = 0; k < K; ++k) {
+      const uint64_t i = base + (uint64_t)k * kInvThreads;
+      fe x = i < n ? fe_load(a + i) : fe_one();
+      if (fe_is_zero(x)) x = fe_one();
+      p[k] = k ? fe_mul(p[k - 1], x) : x;
+    }
+    fe inv = fe_inv_chain(p[K - 1]);
+    const uint64_t last = base + (uint64_t)(K - 1) * kInvThreads;
+    fe x = last < n ? fe_load(a + last) : fe_one();
+#pragma unroll
+    for (uint32_t k = K; k-- > 0;) {
+      const uint64_t i = base + (uint64_t)k * kInvThreads;
+      fe xn = fe_one();  // the next step's input, loaded before this step's store
+      if (k && i - kInvThreads < n) xn = fe_load(a + (i - kInvThreads));
+      if (i < n) {
+        const bool z = fe_is_zero(x);
+        const fe o = k ? fe_mul(inv, p[k - 1]) : inv;
+        fe_store(out + i, z ? fe_zero() : o);
+        if (k && !z) inv = fe_mul(inv, x);
+      }
+      x = xn;
+    }
+  }
+}
+
+hipError_t launch_field_inv(const fe* a, fe* out, uint64_t n, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  const uint64_t chunks = (n + (uint64_t)kInvThreads * kInvK - 1) / ((uint64_t)kInvThreads * kInvK);
+  const uint64_t blocks = chunks < 65536 ? chunks : 65536;
+  hipLaunchKernelGGL(field_inv_kernel, dim3((unsigned)blocks), dim3(kInvThreads), 0, st, a, out, n,
+                     chunks);
+  return hipGetLastError();
+}
+
 }  // namespace mlh

@@ -62,6 +62,82 @@ __global__ __launch_bounds__(kTcThreads) void trace_columns_kernel(
   }
 }
 
+// trace_columns_range_kernel: the same for columns [col0, col0 + ncols) only.
+// A tile is rows x ncols; its elements are no longer contiguous but ncols * 16
+// byte runs at a stride of width * 16 bytes.  Lane e still takes element e of
+// the tile in (row, column) order, (i, j) = (e / ncols, e mod ncols), now at
+// in[(row0 + i) * width + col0 + j]: consecutive lanes read consecutive 16
+// bytes within a run and step to the next row's run after ncols lanes.  (i, j)
+// is carried from load to load (one divide per lane, outside the loops); all
+// of a lane's loads are issued before the first LDS store.  From the LDS store
+// on, the kernel sees a rows x ncols tile and nothing of `width`: slots, pitch
+// (tc_pitch(ncols, R)) and the column read-out are trace_columns_kernel's with
+// ncols for the width.  No element outside the range is read.
+__global__ __launch_bounds__(kTcThreads) void trace_columns_range_kernel(
+    const uint4* __restrict__ in, uint4* __restrict__ out, uint64_t height, uint32_t width,
+    uint32_t col0, uint32_t ncols, uint32_t log_rows, uint32_t pitch, uint64_t tiles) {
+  extern __shared__ uint4 tc_lds[];
+  const uint32_t rows = 1u << log_rows, n = rows * ncols;  // n <= kTcTileElems
+  const uint32_t lane = threadIdx.x;
+  const uint32_t i0 = lane / ncols, j0 = lane - i0 * ncols;
+  const uint32_t di = kTcThreads / ncols, dj = kTcThreads - di * ncols;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t row0 = t << log_rows;
+    const uint4* src = in + row0 * width + col0;
+    uint4 v[kTcPerLane];
+    uint32_t i = i0, j = j0;
+#pragma unroll
+    for (uint32_t k = 0; k < kTcPerLane; ++k) {
+      const uint32_t e = lane + k * kTcThreads;
+      v[k] = e < n ? src[(uint64_t)i * width + j] : uint4{0, 0, 0, 0};
+      i += di;
+      j += dj;
+      if (j >= ncols) {
+        j -= ncols;
+        ++i;
+      }
+    }
+    i = i0;
+    j = j0;
+#pragma unroll
+    for (uint32_t k = 0; k < kTcPerLane; ++k) {
+      const uint32_t e = lane + k * kTcThreads;
+      if (e < n) tc_lds[j * pitch + i] = v[k];
+      i += di;
+      j += dj;
+      if (j >= ncols) {
+        j -= ncols;
+        ++i;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < kTcPerLane; ++k) {
+      const uint32_t e = lane + k * kTcThreads;
+      if (e < n) {
+        const uint32_t c = e >> log_rows, r = e & (rows - 1);
+        out[(uint64_t)c * height + row0 + r] = tc_lds[c * pitch + r];
+      }
+    }
+    __syncthreads();  // the next tile's stores reuse the slots
+  }
+}
+
+hipError_t launch_trace_columns_range(const fe* in, fe* out, uint32_t log_height, uint32_t width,
+                                      uint32_t col0, uint32_t ncols, hipStream_t st) {
+  if (ncols == 0 || col0 >= width || ncols > width - col0) return hipErrorInvalidValue;
+  const uint64_t height = 1ull << log_height;
+  const uint32_t R = tc_tile_rows(ncols);
+  uint32_t log_rows = 0;
+  while ((2ull << log_rows) <= (height < R ? height : R)) ++log_rows;  // rows = min(R, height)
+  const uint64_t tiles = height >> log_rows;
+  const uint32_t pitch = tc_pitch(ncols, R);
+  hipLaunchKernelGGL(trace_columns_range_kernel, dim3(tc_blocks(height, ncols)), dim3(kTcThreads),
+                     (size_t)ncols * pitch * sizeof(uint4), st, reinterpret_cast<const uint4*>(in),
+                     reinterpret_cast<uint4*>(out), height, width, col0, ncols, log_rows, pitch, tiles);
+  return hipGetLastError();
+}
+
 hipError_t launch_trace_columns(const fe* in, fe* out, uint32_t log_height, uint32_t width,
                                 hipStream_t st) {
   const uint64_t height = 1ull << log_height;

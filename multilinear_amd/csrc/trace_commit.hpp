@@ -54,4 +54,15 @@ inline uint32_t tc_blocks(uint64_t height, uint32_t width) {
 hipError_t launch_trace_columns(const fe* in, fe* out, uint32_t log_height, uint32_t width,
                                 hipStream_t st);
 
+// out[j * height + i] = in[i * width + col0 + j], i < height, j < ncols
+// (col0 + ncols <= width): the tile, the pitch and the grid are those of an
+// ncols-wide trace -- tc_tile_rows(ncols), tc_pitch(ncols, R), tc_blocks(height,
+// ncols).  The pitch rule above is a statement about the lane -> (i, j) map and
+// the LDS slot j * pitch + i alone; in the range kernel that map is (e / ncols,
+// e mod ncols), so the rule holds with ncols for W.  What changes with the
+// range is the global side only (runs of ncols * 16 bytes at a stride of
+// width * 16).  Reads nothing outside the range.
+hipError_t launch_trace_columns_range(const fe* in, fe* out, uint32_t log_height, uint32_t width,
+                                      uint32_t col0, uint32_t ncols, hipStream_t st);
+
 }  // namespace mlh

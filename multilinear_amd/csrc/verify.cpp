@@ -466,19 +466,35 @@ mlh_status mlh_system_challenges(mlh_transcript* tr, uint32_t log_rows, uint32_t
   return MLH_OK;
 }
 
+mlh_status mlh_system_trace_randoms(const mlh_transcript* tr, const uint8_t root1[32],
+                                    uint32_t n_randoms, uint8_t* out) {
+  if (!tr || !root1 || (n_randoms && !out)) return MLH_ERR_INVALID;
+  mlh_transcript t = *tr;  // the caller's state stays as it is
+  mlh_transcript_absorb(&t, root1, 32);
+  uint8_t c[16];
+  mlh_transcript_next_challenge(&t, c);  // vec![next_challenge(); n] (system.rs:139)
+  for (uint32_t i = 0; i < n_randoms; ++i) memcpy(out + 16ull * i, c, 16);
+  return MLH_OK;
+}
+
 }  // extern "C"
 
 // System::verify_with_evaluations (sumcheck.rs:91-124); rs_out (optional)
 // receives the challenges it derives.
+// smask / beta: the sum columns' term (mlh_cs_sumcheck_verify_sums); sum is
+// then the combined claim.
 static mlh_status cs_sumcheck_verify_rs(const mlh_cs_program* prog, uint32_t log_height,
                                         const uint8_t* host_row_points, const uint8_t* host_randoms,
-                                        const uint8_t* host_mask, const uint8_t sum[16],
-                                        const uint8_t* polys, const uint8_t* host_output,
-                                        mlh_transcript* tr, std::vector<u128>* rs_out) {
+                                        const uint8_t* host_mask, uint32_t smask, const uint8_t* beta,
+                                        const uint8_t sum[16], const uint8_t* polys,
+                                        const uint8_t* host_output, mlh_transcript* tr,
+                                        std::vector<u128>* rs_out) {
   if (!prog || !host_row_points || !host_mask || !sum || !polys || !host_output || !tr ||
       log_height < 1 || log_height > kCsMaxLogHeight || (prog->p.n_randoms && !host_randoms))
     return MLH_ERR_INVALID;
   const CsProgram& P = prog->p;
+  if (smask && (!beta || h_load(beta) >= kModulus || (P.width < 32 && (smask >> P.width))))
+    return MLH_ERR_INVALID;
   const uint32_t L = log_height, D = P.points();
   std::vector<u128> row, rnd, mask, output, co;
   if (!load_canonical(host_row_points, L, row) || !load_canonical(host_randoms, P.n_randoms, rnd) ||
@@ -508,7 +524,13 @@ static mlh_status cs_sumcheck_verify_rs(const mlh_cs_program* prog, uint32_t log
   for (uint32_t i = 0; i < L; ++i)
     delta = h_mul(delta, h_add(h_mul(row[i], rs[i]), h_mul(h_sub(1, row[i]), h_sub(1, rs[i]))));
   const u128 comp = cs_host_eval(P, output.data(), rnd.data(), mask.data());
-  if (h_mul(delta, comp) != claim) {  // :119-123
+  u128 lin = 0;  // beta * sum_{j in S} output[j]
+  if (smask) {
+    for (uint32_t j = 0; j < P.width; ++j)
+      if ((smask >> j) & 1u) lin = h_add(lin, output[j]);
+    lin = h_mul(lin, h_load(beta));
+  }
+  if (h_add(h_mul(delta, comp), lin) != claim) {  // :119-123
     tr->sha = saved;
     return MLH_ERR_VERIFY;
   }
@@ -523,8 +545,18 @@ mlh_status mlh_cs_sumcheck_verify(const mlh_cs_program* prog, uint32_t log_heigh
                                   const uint8_t* host_mask, const uint8_t sum[16],
                                   const uint8_t* polys, const uint8_t* host_output,
                                   mlh_transcript* tr) {
-  return cs_sumcheck_verify_rs(prog, log_height, host_row_points, host_randoms, host_mask, sum,
-                               polys, host_output, tr, nullptr);
+  return cs_sumcheck_verify_rs(prog, log_height, host_row_points, host_randoms, host_mask, 0, nullptr,
+                               sum, polys, host_output, tr, nullptr);
+}
+
+mlh_status mlh_cs_sumcheck_verify_sums(const mlh_cs_program* prog, uint32_t log_height,
+                                       const uint8_t* host_row_points, const uint8_t* host_randoms,
+                                       const uint8_t* host_mask, uint32_t sum_column_mask,
+                                       const uint8_t* beta, const uint8_t claim[16],
+                                       const uint8_t* polys, const uint8_t* host_output,
+                                       mlh_transcript* tr) {
+  return cs_sumcheck_verify_rs(prog, log_height, host_row_points, host_randoms, host_mask,
+                               sum_column_mask, beta, claim, polys, host_output, tr, nullptr);
 }
 
 mlh_status mlh_system_verify(const mlh_cs_program* prog, uint32_t log_height, const uint8_t sum[16],
@@ -550,12 +582,70 @@ mlh_status mlh_system_verify(const mlh_cs_program* prog, uint32_t log_height, co
   // 3. the sumcheck against the claimed output; 4. the opening at its rs
   std::vector<u128> rs;
   if (st == MLH_OK)
-    st = cs_sumcheck_verify_rs(prog, L, row.data(), rnd.data(), mask.data(), sum,
+    st = cs_sumcheck_verify_rs(prog, L, row.data(), rnd.data(), mask.data(), 0, nullptr, sum,
                                proof->sumcheck_polys, proof->output, tr, &rs);
   if (st == MLH_OK) {
     std::vector<uint8_t> in(16ull * L);
     for (uint32_t i = 0; i < L; ++i) h_store(in.data() + 16ull * i, rs[i]);
     st = mlh_batched_pcs_verify(&proof->pcs, L, in.data(), proof->output, tr);
+  }
+  if (st != MLH_OK) {
+    tr->sha = saved;
+    return MLH_ERR_VERIFY;
+  }
+  return MLH_OK;
+}
+
+mlh_status mlh_system_verify_phased(const mlh_cs_program* prog, uint32_t log_height,
+                                    uint32_t pre_random_columns, uint32_t sum_column_mask,
+                                    const uint8_t sum[16], const uint8_t column_sum[16],
+                                    const mlh_phased_proof* proof, mlh_transcript* tr) {
+  if (!prog || !sum || !column_sum || !proof || !tr || !proof->sumcheck_polys || !proof->output ||
+      !proof->pcs[0].sumcheck_polys)
+    return MLH_ERR_INVALID;
+  const CsProgram& P = prog->p;
+  const uint32_t L = log_height, W = P.width, P1 = pre_random_columns;
+  if (L < 1 || L > kCsMaxLogHeight || P1 < 1 || P1 > W || (W < 32 && (sum_column_mask >> W)) ||
+      proof->log_height != L || proof->width != W || proof->degree != P.degree ||
+      proof->pre_random_columns != P1 || proof->sum_column_mask != sum_column_mask ||
+      proof->pcs[0].fri.num_codes != P1 ||
+      (P1 < W && (!proof->pcs[1].sumcheck_polys || proof->pcs[1].fri.num_codes != W - P1)) ||
+      h_load(sum) >= kModulus || h_load(column_sum) >= kModulus)
+    return MLH_ERR_VERIFY;
+  const mlh::HostSha256 saved = tr->sha;
+  // 1. root 1; 2. the trace randoms; 3. root 2; 4. the other challenges and the mask
+  mlh_transcript_absorb(tr, proof->pcs[0].fri.batch_commitment, 32);
+  uint32_t log_nc = 0;
+  while ((1ull << log_nc) < P.n_constraints) ++log_nc;
+  std::vector<uint8_t> row(16ull * L), rnd(16ull * P.n_randoms + 16), cons(16ull * log_nc + 16),
+      mask(16ull * P.n_constraints);
+  {
+    uint8_t c[16];
+    mlh_transcript_next_challenge(tr, c);
+    for (uint32_t i = 0; i < P.n_randoms; ++i) memcpy(rnd.data() + 16ull * i, c, 16);
+  }
+  if (P1 < W) mlh_transcript_absorb(tr, proof->pcs[1].fri.batch_commitment, 32);
+  mlh_status st = mlh_system_challenges(tr, L, 0, P.n_constraints, row.data(), nullptr, cons.data(),
+                                        mask.data());
+  // 5. beta and the combined claim
+  uint8_t beta[16] = {0}, claim[16];
+  memcpy(claim, sum, 16);
+  if (sum_column_mask) {
+    mlh_transcript_absorb(tr, column_sum, 16);
+    mlh_transcript_next_challenge(tr, beta);
+    h_store(claim, h_add(h_load(sum), h_mul(h_load(beta), h_load(column_sum))));
+  }
+  // 6. the sumcheck against the claimed output; 7., 8. the openings at its rs
+  std::vector<u128> rs;
+  if (st == MLH_OK)
+    st = cs_sumcheck_verify_rs(prog, L, row.data(), rnd.data(), mask.data(), sum_column_mask, beta,
+                               claim, proof->sumcheck_polys, proof->output, tr, &rs);
+  if (st == MLH_OK) {
+    std::vector<uint8_t> in(16ull * L);
+    for (uint32_t i = 0; i < L; ++i) h_store(in.data() + 16ull * i, rs[i]);
+    st = mlh_batched_pcs_verify(&proof->pcs[0], L, in.data(), proof->output, tr);
+    if (st == MLH_OK && P1 < W)
+      st = mlh_batched_pcs_verify(&proof->pcs[1], L, in.data(), proof->output + 16ull * P1, tr);
   }
   if (st != MLH_OK) {
     tr->sha = saved;
