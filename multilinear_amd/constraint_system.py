@@ -373,24 +373,29 @@ class Commitment:
         return bytes(out)
 
 
-class SystemProof:
-    """mlh_system_proof: the sumcheck polynomials, Trace::evaluate(rs) and the
-    batched-PCS opening of the committed columns at rs."""
+def _program_of(constraints, layout):
+    return Program(compile_program(constraints.constraints(), layout.columns, layout.randoms,
+                                   constraints.degree()))
 
-    def __init__(self, log_height, width, degree):
+
+class _ProofHolder:
+    """What SystemProof and PhasedSystemProof share: the header, the buffers of
+    the sumcheck polynomials and of Trace::evaluate(rs) behind the C struct
+    ``c``, and their views."""
+
+    def __init__(self, c, log_height, width, degree):
         self.log_height, self.width, self.degree = log_height, width, degree
         self._polys = (ctypes.c_uint8 * (16 * (degree + 1) * log_height))()
         self._output = (ctypes.c_uint8 * (16 * width))()
-        self.pcs = BatchedPCSProof(log_height, width)
-        self.c = _lib.SystemProofC()
-        self.c.log_height, self.c.width, self.c.degree = log_height, width, degree
-        self.c.sumcheck_polys = ctypes.cast(self._polys, ctypes.c_void_p)
-        self.c.output = ctypes.cast(self._output, ctypes.c_void_p)
-        self.c.pcs = self.pcs.c
+        self.c = c
+        c.log_height, c.width, c.degree = log_height, width, degree
+        c.sumcheck_polys = ctypes.cast(self._polys, ctypes.c_void_p)
+        c.output = ctypes.cast(self._output, ctypes.c_void_p)
 
     def _sync(self):  # the struct holds copies of the nested ones
-        self.pcs.c = self.c.pcs
-        self.pcs.fri_proof.c = self.c.pcs.fri
+        for p, c in self._nested():
+            p.c = c
+            p.fri_proof.c = c.fri
 
     @property
     def sumcheck_polynomials(self):
@@ -402,6 +407,19 @@ class SystemProof:
     def output(self):
         return _split(self._output, self.width)
 
+
+class SystemProof(_ProofHolder):
+    """mlh_system_proof: the sumcheck polynomials, Trace::evaluate(rs) and the
+    batched-PCS opening of the committed columns at rs."""
+
+    def __init__(self, log_height, width, degree):
+        super().__init__(_lib.SystemProofC(), log_height, width, degree)
+        self.pcs = BatchedPCSProof(log_height, width)
+        self.c.pcs = self.pcs.c
+
+    def _nested(self):
+        return [(self.pcs, self.c.pcs)]
+
     @property
     def commitment(self):
         return bytes(self.c.pcs.fri.batch_commitment)
@@ -409,8 +427,7 @@ class SystemProof:
     def verify(self, transcript, constraints, layout, total_sum):
         """mlh_system_verify, host only: True iff accepted.  The transcript
         is the one the prover started from; it is advanced only on True."""
-        prog = Program(compile_program(constraints.constraints(), layout.columns, layout.randoms,
-                                       constraints.degree()))
+        prog = _program_of(constraints, layout)
         return lib().mlh_system_verify(prog.h, self.log_height, fe_bytes(total_sum),
                                        ctypes.byref(self.c), transcript.h) == 0
 
@@ -424,41 +441,23 @@ def _column_mask(layout):
     return m
 
 
-class PhasedSystemProof:
+class PhasedSystemProof(_ProofHolder):
     """mlh_phased_proof: the sumcheck polynomials, Trace::evaluate(rs) and the
     openings of the two commitments (columns [0, P) and [P, W)) at rs."""
 
     def __init__(self, log_height, width, degree, pre_random_columns, sum_column_mask):
-        self.log_height, self.width, self.degree = log_height, width, degree
+        super().__init__(_lib.PhasedProofC(), log_height, width, degree)
         self.pre_random_columns, self.sum_column_mask = pre_random_columns, sum_column_mask
-        self._polys = (ctypes.c_uint8 * (16 * (degree + 1) * log_height))()
-        self._output = (ctypes.c_uint8 * (16 * width))()
         P = pre_random_columns
         self.pcs = [BatchedPCSProof(log_height, P)]
         if P < width:
             self.pcs.append(BatchedPCSProof(log_height, width - P))
-        self.c = _lib.PhasedProofC()
-        self.c.log_height, self.c.width, self.c.degree = log_height, width, degree
         self.c.pre_random_columns, self.c.sum_column_mask = P, sum_column_mask
-        self.c.sumcheck_polys = ctypes.cast(self._polys, ctypes.c_void_p)
-        self.c.output = ctypes.cast(self._output, ctypes.c_void_p)
         for i, p in enumerate(self.pcs):
             self.c.pcs[i] = p.c
 
-    def _sync(self):  # the struct holds copies of the nested ones
-        for i, p in enumerate(self.pcs):
-            p.c = self.c.pcs[i]
-            p.fri_proof.c = self.c.pcs[i].fri
-
-    @property
-    def sumcheck_polynomials(self):
-        D = self.degree + 1
-        flat = _split(self._polys, D * self.log_height)
-        return [flat[D * k:D * k + D] for k in range(self.log_height)]
-
-    @property
-    def output(self):
-        return _split(self._output, self.width)
+    def _nested(self):
+        return [(p, self.c.pcs[i]) for i, p in enumerate(self.pcs)]
 
     @property
     def commitments(self):
@@ -468,8 +467,7 @@ class PhasedSystemProof:
         """mlh_system_verify_phased, host only: True iff accepted.  The
         transcript is the one the prover started from; it is advanced only on
         True."""
-        prog = Program(compile_program(constraints.constraints(), layout.columns, layout.randoms,
-                                       constraints.degree()))
+        prog = _program_of(constraints, layout)
         return lib().mlh_system_verify_phased(prog.h, self.log_height, layout.pre_random_columns,
                                               _column_mask(layout), fe_bytes(total_sum),
                                               fe_bytes(column_sum), ctypes.byref(self.c),
@@ -488,8 +486,7 @@ class PhasedProver:
             raise ValueError("pre_random_columns must be in 1..columns, columns the trace's width")
         self._constraints, self._layout, self._trace, self._device = constraints, layout, trace, device
         self._mask = _column_mask(layout)
-        self.program = Program(compile_program(constraints.constraints(), W, layout.randoms,
-                                               constraints.degree()))
+        self.program = _program_of(constraints, layout)
         self._com1 = Commitment.new(trace, device, columns=(0, P))
         out = (ctypes.c_uint8 * (16 * max(layout.randoms, 1)))()
         check(lib().mlh_system_trace_randoms(transcript.h, self._com1.root(), layout.randoms, out))
@@ -566,8 +563,7 @@ class System:
         n = len(constraints.constraints())
         self._challenges = ChallengeSet(transcript, layout.randoms, n, log_num_rows)
         self._constraint_mask = self._challenges.mask
-        self.program = Program(compile_program(constraints.constraints(), layout.columns,
-                                               layout.randoms, constraints.degree()))
+        self.program = _program_of(constraints, layout)
 
     @staticmethod
     def prover(transcript, constraints, layout, trace, device=0):  # system.rs:56-72

@@ -37,6 +37,7 @@
 #include "ntt.hpp"
 #include "sha256.hpp"
 #include "sumcheck.hpp"
+#include "system_head.hpp"
 #include "trace_commit.hpp"
 #include "transcript_dev.hpp"
 
@@ -2602,67 +2603,49 @@ struct mlh_trace_commitment {
   }
 };
 
-extern "C" {
-
-mlh_status mlh_trace_columns(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
-                             uint32_t width, void* dev_out) {
-  if (!ctx || !dev_matrix || !dev_out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (width < 1 || width > kCsMaxWidth || log_height > kCsMaxLogHeight)
-    return fail(ctx, MLH_ERR_INVALID, "width 1..32, log_height 0..32");
-  if (ranges_overlap(dev_matrix, dev_out, ((uint64_t)width << log_height) * 16))
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_columns is out of place: the buffers overlap");
-  ProfScope ps(ctx, "trace_columns");
-  HIP_TRY(ctx, launch_trace_columns(reinterpret_cast<const fe*>(dev_matrix),
-                                    reinterpret_cast<fe*>(dev_out), log_height, width, ctx->stream));
-  ps.end();
-  return MLH_OK;
+static bool trace_range_ok(uint32_t log_height, uint32_t width, uint32_t col0, uint32_t ncols) {
+  return width >= 1 && width <= kCsMaxWidth && log_height <= kCsMaxLogHeight && ncols >= 1 &&
+         col0 < width && ncols <= width - col0;
 }
 
-mlh_status mlh_trace_columns_launch_info(uint32_t log_height, uint32_t width, uint32_t* tile_rows,
-                                         uint32_t* blocks) {
-  if (!tile_rows || !blocks || width < 1 || width > kCsMaxWidth || log_height > kCsMaxLogHeight)
-    return MLH_ERR_INVALID;
-  *tile_rows = tc_tile_rows(width);
-  *blocks = tc_blocks(1ull << log_height, width);
-  return MLH_OK;
-}
-
-mlh_status mlh_trace_columns_range(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
-                                   uint32_t width, uint32_t col0, uint32_t ncols, void* dev_out) {
+// mlh_trace_columns (col0 = 0, ncols = width) and mlh_trace_columns_range.
+// dev_out holds ncols columns and the trace is read over its whole extent; for
+// the whole width that is the plain overlap rule.
+static mlh_status trace_columns_impl(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                     uint32_t width, uint32_t col0, uint32_t ncols, void* dev_out) {
   if (!ctx || !dev_matrix || !dev_out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (width < 1 || width > kCsMaxWidth || log_height > kCsMaxLogHeight)
-    return fail(ctx, MLH_ERR_INVALID, "width 1..32, log_height 0..32");
-  if (ncols < 1 || col0 >= width || ncols > width - col0)
-    return fail(ctx, MLH_ERR_INVALID, "column range outside the trace");
-  // dev_out holds ncols columns; the trace is read over its whole extent
+  if (!trace_range_ok(log_height, width, col0, ncols))
+    return fail(ctx, MLH_ERR_INVALID,
+                "width 1..32, log_height 0..32, a column range inside the trace");
   const uint64_t tb = ((uint64_t)width << log_height) * 16, ob = ((uint64_t)ncols << log_height) * 16;
   const uintptr_t x = (uintptr_t)dev_matrix, y = (uintptr_t)dev_out;
   if (x < y ? y - x < tb : x - y < ob)
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_columns_range is out of place: the buffers overlap");
-  ProfScope ps(ctx, "trace_columns_range");
-  HIP_TRY(ctx, launch_trace_columns_range(reinterpret_cast<const fe*>(dev_matrix),
-                                          reinterpret_cast<fe*>(dev_out), log_height, width, col0,
-                                          ncols, ctx->stream));
+    return fail(ctx, MLH_ERR_INVALID, "the trace transpose is out of place: the buffers overlap");
+  ProfScope ps(ctx, ncols == width ? "trace_columns" : "trace_columns_range");
+  HIP_TRY(ctx, launch_trace_columns(reinterpret_cast<const fe*>(dev_matrix),
+                                    reinterpret_cast<fe*>(dev_out), log_height, width, col0, ncols,
+                                    ctx->stream));
   ps.end();
   return MLH_OK;
 }
 
-mlh_status mlh_trace_columns_range_launch_info(uint32_t log_height, uint32_t width, uint32_t col0,
-                                               uint32_t ncols, uint32_t* tile_rows,
-                                               uint32_t* blocks) {
-  if (!tile_rows || !blocks || width < 1 || width > kCsMaxWidth || log_height > kCsMaxLogHeight ||
-      ncols < 1 || col0 >= width || ncols > width - col0)
+static mlh_status trace_launch_info(uint32_t log_height, uint32_t width, uint32_t col0,
+                                    uint32_t ncols, uint32_t* tile_rows, uint32_t* blocks) {
+  if (!tile_rows || !blocks || !trace_range_ok(log_height, width, col0, ncols))
     return MLH_ERR_INVALID;
   *tile_rows = tc_tile_rows(ncols);
   *blocks = tc_blocks(1ull << log_height, ncols);
   return MLH_OK;
 }
 
-// Commitment::new over columns [col0, col0 + ncols); full = mlh_trace_commit's
-// own path (mlh_trace_columns, one contiguous tile per block).
+// Commitment::new over columns [col0, col0 + ncols)
 static mlh_status trace_commit_impl(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
-                                    uint32_t width, uint32_t col0, uint32_t ncols, bool full,
+                                    uint32_t width, uint32_t col0, uint32_t ncols,
                                     mlh_trace_commitment** out) {
+  if (!ctx || !dev_matrix || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (log_height < 1 || !trace_range_ok(log_height, width, col0, ncols))
+    return fail(ctx, MLH_ERR_INVALID,
+                "width 1..32, log_height 1..32, a column range inside the trace");
   std::unique_ptr<mlh_trace_commitment> c(new mlh_trace_commitment());
   c->ctx = ctx;
   c->log_height = log_height;
@@ -2671,10 +2654,7 @@ static mlh_status trace_commit_impl(mlh_ctx* ctx, const void* dev_matrix, uint32
   MLH_TRY(pool_alloc(ctx, ncols * n * 16, &c->evals));
   MLH_TRY(pool_alloc(ctx, ncols * n * 32, &c->codes));
   MLH_TRY(pool_alloc(ctx, mlh_merkle_layers_bytes(n), &c->tree));
-  if (full)
-    MLH_TRY(mlh_trace_columns(ctx, dev_matrix, log_height, width, c->evals));
-  else
-    MLH_TRY(mlh_trace_columns_range(ctx, dev_matrix, log_height, width, col0, ncols, c->evals));
+  MLH_TRY(trace_columns_impl(ctx, dev_matrix, log_height, width, col0, ncols, c->evals));
   fe* codes = reinterpret_cast<fe*>(c->codes);
   MLH_TRY(batched_pcs_codes(ctx, c->evals, ncols, log_height, codes));
   // the batch layer of BatchedFriProverData::init (batched_fri.rs:41-81)
@@ -2686,23 +2666,38 @@ static mlh_status trace_commit_impl(mlh_ctx* ctx, const void* dev_matrix, uint32
   return MLH_OK;
 }
 
+extern "C" {
+
+mlh_status mlh_trace_columns(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                             uint32_t width, void* dev_out) {
+  return trace_columns_impl(ctx, dev_matrix, log_height, width, 0, width, dev_out);
+}
+
+mlh_status mlh_trace_columns_launch_info(uint32_t log_height, uint32_t width, uint32_t* tile_rows,
+                                         uint32_t* blocks) {
+  return trace_launch_info(log_height, width, 0, width, tile_rows, blocks);
+}
+
+mlh_status mlh_trace_columns_range(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                   uint32_t width, uint32_t col0, uint32_t ncols, void* dev_out) {
+  return trace_columns_impl(ctx, dev_matrix, log_height, width, col0, ncols, dev_out);
+}
+
+mlh_status mlh_trace_columns_range_launch_info(uint32_t log_height, uint32_t width, uint32_t col0,
+                                               uint32_t ncols, uint32_t* tile_rows,
+                                               uint32_t* blocks) {
+  return trace_launch_info(log_height, width, col0, ncols, tile_rows, blocks);
+}
+
 mlh_status mlh_trace_commit(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
                             uint32_t width, mlh_trace_commitment** out) {
-  if (!ctx || !dev_matrix || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (width < 1 || width > kCsMaxWidth || log_height < 1 || log_height > kCsMaxLogHeight)
-    return fail(ctx, MLH_ERR_INVALID, "width 1..32, log_height 1..32");
-  return trace_commit_impl(ctx, dev_matrix, log_height, width, 0, width, true, out);
+  return trace_commit_impl(ctx, dev_matrix, log_height, width, 0, width, out);
 }
 
 mlh_status mlh_trace_commit_range(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
                                   uint32_t width, uint32_t col0, uint32_t ncols,
                                   mlh_trace_commitment** out) {
-  if (!ctx || !dev_matrix || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (width < 1 || width > kCsMaxWidth || log_height < 1 || log_height > kCsMaxLogHeight)
-    return fail(ctx, MLH_ERR_INVALID, "width 1..32, log_height 1..32");
-  if (ncols < 1 || col0 >= width || ncols > width - col0)
-    return fail(ctx, MLH_ERR_INVALID, "column range outside the trace");
-  return trace_commit_impl(ctx, dev_matrix, log_height, width, col0, ncols, false, out);
+  return trace_commit_impl(ctx, dev_matrix, log_height, width, col0, ncols, out);
 }
 
 mlh_status mlh_trace_commitment_root(const mlh_trace_commitment* c, uint8_t out[32]) {
@@ -3072,21 +3067,57 @@ mlh_status mlh_cs_sumcheck_prove_sums(mlh_ctx* ctx, const mlh_cs_program* prog, 
 // ChallengeSet -> constraint sumcheck -> batched PCS opening of the committed
 // columns at the sumcheck's point.
 // ---------------------------------------------------------------------------
-// Restores the caller's transcript to its state at construction unless keep()
-// was called: a failed prove leaves it untouched (mlhip.h), the root absorbed
-// first included.
-struct TranscriptGuard {
-  mlh_transcript* tr;
-  mlh::HostSha256 saved;
-  bool kept = false;
-  explicit TranscriptGuard(mlh_transcript* t) : tr(t), saved(t->sha) {}
-  TranscriptGuard(const TranscriptGuard&) = delete;
-  TranscriptGuard& operator=(const TranscriptGuard&) = delete;
-  ~TranscriptGuard() {
-    if (!kept) tr->sha = saved;
+// What follows the argument checks of both system provers: the transcript
+// head, delta = eq(row), the sumcheck rounds, output = row 0 of the folded
+// matrix, then BatchedPCSProof::prove(inputs = rs, outputs = output) on each
+// handle's codes, evaluations and batch tree -- com1 for its columns into pcs1,
+// com2 (null: one phase) for the rest into pcs2.  A failure leaves the
+// transcript as at entry, the root absorbed first included.
+static mlh_status system_prove_core(mlh_ctx* ctx, const mlh_cs_program* prog,
+                                    const mlh_trace_commitment* com1,
+                                    const mlh_trace_commitment* com2, uint32_t sum_column_mask,
+                                    void* dev_matrix, const uint8_t sum[16],
+                                    const uint8_t* column_sum, mlh_transcript* tr,
+                                    uint8_t* polys_out, uint8_t* output_out,
+                                    mlh_batched_pcs_proof* pcs1, mlh_batched_pcs_proof* pcs2) {
+  const uint32_t L = com1->log_height, W = prog->p.width;
+  TranscriptGuard guard(tr);
+  SystemHead h(prog->p, L);
+  if (system_head(tr, prog->p, L, com1->root, com2 ? com2->root : nullptr, sum_column_mask, sum,
+                  column_sum, &h) != MLH_OK)
+    return fail(ctx, MLH_ERR_INVALID, "challenge set");
+  PoolBuf delta(ctx);
+  MLH_TRY(delta.alloc(16ull << L));
+  MLH_TRY(mlh_eq_table(ctx, h.row.data(), L, delta.p));
+  std::vector<uint8_t> rs(16ull * L);
+  {
+    ProfScope ps(ctx, "system_sumcheck");
+    MLH_TRY(mlh_cs_sumcheck_prove_sums(ctx, prog, W, dev_matrix, delta.p, L, h.randoms.data(),
+                                       h.mask.data(), sum_column_mask, h.beta, h.claim, tr,
+                                       polys_out, rs.data()));
+    ps.end();
   }
-  void keep() { kept = true; }
-};
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev_matrix, 16ull * W, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<uint8_t> output(ctx->pinned, ctx->pinned + 16ull * W);
+  {
+    ProfScope ps(ctx, "system_open");
+    MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com1->codes), com1->evals,
+                             reinterpret_cast<const uint8_t*>(com1->tree), com1->width, L, rs.data(),
+                             output.data(), tr, pcs1));
+    ps.end();
+  }
+  if (com2) {
+    ProfScope ps(ctx, "system_open2");
+    MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com2->codes), com2->evals,
+                             reinterpret_cast<const uint8_t*>(com2->tree), com2->width, L, rs.data(),
+                             output.data() + 16ull * com1->width, tr, pcs2));
+    ps.end();
+  }
+  memcpy(output_out, output.data(), output.size());
+  guard.keep();
+  return MLH_OK;
+}
 
 extern "C" {
 
@@ -3100,45 +3131,11 @@ mlh_status mlh_system_prove(mlh_ctx* ctx, const mlh_cs_program* prog,
   if (prog->p.width != com->width)
     return fail(ctx, MLH_ERR_INVALID, "program width differs from the commitment's");
   if (h_load(sum) >= kModulus) return fail(ctx, MLH_ERR_INVALID, "non-canonical sum");
-  const CsProgram& P = prog->p;
-  const uint32_t L = com->log_height, W = com->width;
-  TranscriptGuard guard(tr);
-  // 1. the commitment, where system.rs:62-63 makes it; 2. ChallengeSet::new
-  mlh_transcript_absorb(tr, com->root, 32);
-  uint32_t log_nc = 0;
-  while ((1ull << log_nc) < P.n_constraints) ++log_nc;
-  std::vector<uint8_t> row(16ull * L), rnd(16ull * P.n_randoms + 16), cons(16ull * log_nc + 16),
-      mask(16ull * P.n_constraints), rs(16ull * L);
-  if (mlh_system_challenges(tr, L, P.n_randoms, P.n_constraints, row.data(), rnd.data(),
-                            cons.data(), mask.data()) != MLH_OK)
-    return fail(ctx, MLH_ERR_INVALID, "challenge set");
-  // 3. delta = eq(row), the sumcheck rounds; output = row 0 of the folded matrix
-  PoolBuf delta(ctx);
-  MLH_TRY(delta.alloc(16ull << L));
-  MLH_TRY(mlh_eq_table(ctx, row.data(), L, delta.p));
-  {
-    ProfScope ps(ctx, "system_sumcheck");
-    MLH_TRY(mlh_cs_sumcheck_prove(ctx, prog, W, dev_matrix, delta.p, L, rnd.data(), mask.data(), sum,
-                                  tr, proof->sumcheck_polys, rs.data()));
-    ps.end();
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev_matrix, 16ull * W, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<uint8_t> output(ctx->pinned, ctx->pinned + 16ull * W);
-  // 4. BatchedPCSProof::prove(inputs = rs, outputs = output) on the committed
-  // codes, evaluations and batch tree
-  {
-    ProfScope ps(ctx, "system_open");
-    MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com->codes), com->evals,
-                             reinterpret_cast<const uint8_t*>(com->tree), W, L, rs.data(),
-                             output.data(), tr, &proof->pcs));
-    ps.end();
-  }
-  memcpy(proof->output, output.data(), output.size());
-  proof->log_height = L;
-  proof->width = W;
-  proof->degree = P.degree;
-  guard.keep();
+  MLH_TRY(system_prove_core(ctx, prog, com, nullptr, 0, dev_matrix, sum, nullptr, tr,
+                            proof->sumcheck_polys, proof->output, &proof->pcs, nullptr));
+  proof->log_height = com->log_height;
+  proof->width = com->width;
+  proof->degree = prog->p.degree;
   return MLH_OK;
 }
 
@@ -3155,9 +3152,8 @@ mlh_status mlh_system_prove_phased(mlh_ctx* ctx, const mlh_cs_program* prog,
     return fail(ctx, MLH_ERR_INVALID, "null argument");
   if (com1->ctx != ctx || (com2 && com2->ctx != ctx))
     return fail(ctx, MLH_ERR_INVALID, "commitment of another context");
-  const CsProgram& P = prog->p;
-  const uint32_t L = com1->log_height, W = P.width, P1 = com1->width, P2 = com2 ? com2->width : 0;
-  if (P1 < 1 || P1 + P2 != W || (com2 && com2->log_height != L))
+  const uint32_t W = prog->p.width, P1 = com1->width, P2 = com2 ? com2->width : 0;
+  if (P1 < 1 || P1 + P2 != W || (com2 && com2->log_height != com1->log_height))
     return fail(ctx, MLH_ERR_INVALID,
                 "the commitments' widths must add up to the program's (com2 null iff all columns "
                 "are pre-random), over the same rows");
@@ -3165,67 +3161,13 @@ mlh_status mlh_system_prove_phased(mlh_ctx* ctx, const mlh_cs_program* prog,
     return fail(ctx, MLH_ERR_INVALID, "sum column at or above the width");
   if (h_load(sum) >= kModulus || h_load(column_sum) >= kModulus)
     return fail(ctx, MLH_ERR_INVALID, "non-canonical sum");
-  TranscriptGuard guard(tr);
-  // 1. root 1; 2. the trace randoms (ChallengeSet::new's trace, system.rs:139); 3. root 2;
-  // 4. the row and constraint challenges and the mask
-  mlh_transcript_absorb(tr, com1->root, 32);
-  uint32_t log_nc = 0;
-  while ((1ull << log_nc) < P.n_constraints) ++log_nc;
-  std::vector<uint8_t> row(16ull * L), rnd(16ull * P.n_randoms + 16), cons(16ull * log_nc + 16),
-      mask(16ull * P.n_constraints), rs(16ull * L);
-  {
-    uint8_t c[16];
-    mlh_transcript_next_challenge(tr, c);
-    for (uint32_t i = 0; i < P.n_randoms; ++i) memcpy(rnd.data() + 16ull * i, c, 16);
-  }
-  if (com2) mlh_transcript_absorb(tr, com2->root, 32);
-  if (mlh_system_challenges(tr, L, 0, P.n_constraints, row.data(), nullptr, cons.data(),
-                            mask.data()) != MLH_OK)
-    return fail(ctx, MLH_ERR_INVALID, "challenge set");
-  // 5. beta after the claimed column sum; the combined claim
-  uint8_t beta[16] = {0}, claim[16];
-  memcpy(claim, sum, 16);
-  if (sum_column_mask) {
-    mlh_transcript_absorb(tr, column_sum, 16);
-    mlh_transcript_next_challenge(tr, beta);
-    h_store(claim, h_add(h_load(sum), h_mul(h_load(beta), h_load(column_sum))));
-  }
-  // 6. the sumcheck; output = row 0 of the folded matrix
-  PoolBuf delta(ctx);
-  MLH_TRY(delta.alloc(16ull << L));
-  MLH_TRY(mlh_eq_table(ctx, row.data(), L, delta.p));
-  {
-    ProfScope ps(ctx, "system_sumcheck");
-    MLH_TRY(mlh_cs_sumcheck_prove_sums(ctx, prog, W, dev_matrix, delta.p, L, rnd.data(), mask.data(),
-                                       sum_column_mask, beta, claim, tr, proof->sumcheck_polys,
-                                       rs.data()));
-    ps.end();
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev_matrix, 16ull * W, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<uint8_t> output(ctx->pinned, ctx->pinned + 16ull * W);
-  // 7., 8. the openings, each on its handle's codes, evaluations and batch tree
-  {
-    ProfScope ps(ctx, "system_open");
-    MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com1->codes), com1->evals,
-                             reinterpret_cast<const uint8_t*>(com1->tree), P1, L, rs.data(),
-                             output.data(), tr, &proof->pcs[0]));
-    ps.end();
-  }
-  if (com2) {
-    ProfScope ps(ctx, "system_open2");
-    MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com2->codes), com2->evals,
-                             reinterpret_cast<const uint8_t*>(com2->tree), P2, L, rs.data(),
-                             output.data() + 16ull * P1, tr, &proof->pcs[1]));
-    ps.end();
-  }
-  memcpy(proof->output, output.data(), output.size());
-  proof->log_height = L;
+  MLH_TRY(system_prove_core(ctx, prog, com1, com2, sum_column_mask, dev_matrix, sum, column_sum, tr,
+                            proof->sumcheck_polys, proof->output, &proof->pcs[0], &proof->pcs[1]));
+  proof->log_height = com1->log_height;
   proof->width = W;
-  proof->degree = P.degree;
+  proof->degree = prog->p.degree;
   proof->pre_random_columns = P1;
   proof->sum_column_mask = sum_column_mask;
-  guard.keep();
   return MLH_OK;
 }
 

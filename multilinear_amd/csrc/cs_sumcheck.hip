@@ -132,18 +132,25 @@ __device__ __forceinline__ void cs_block_sum(fe v, uint32_t B, fe* red, fe* __re
   __syncthreads();
 }
 
-// partials[t * gridDim.x + blockIdx.x] = the block's sum t
-__device__ __forceinline__ void cs_block_sums(const CsDev& P, const fe* lane_lds, uint32_t B,
-                                              fe* __restrict__ partials) {
+__device__ __forceinline__ void cs_zero_sums(const CsDev& P, fe* lane_lds, uint32_t B) {
+  const uint32_t acc0 = 2 * P.width + P.n_temps;
+  for (uint32_t t = 0; t < P.D; ++t) lane_lds[(acc0 + t) * B] = fe_zero();
+}
+
+// The end of both bodies: partials[t * gridDim.x + block] = the block's sum t; SUMS: its A and
+// B into lin[block] and lin[gridDim.x + block], reduced in the caller's lred (4 elements of LDS).
+template <bool SUMS>
+__device__ __forceinline__ void cs_write_sums(const CsDev& P, const fe* lane_lds, uint32_t B,
+                                              fe* __restrict__ partials, const fe& la, const fe& lb,
+                                              fe* lred, fe* __restrict__ lin) {
   __shared__ fe red[4];
   const uint32_t acc0 = 2 * P.width + P.n_temps;
   for (uint32_t t = 0; t < P.D; ++t)
     cs_block_sum(lane_lds[(acc0 + t) * B], B, red, partials + (uint64_t)t * gridDim.x + blockIdx.x);
-}
-
-__device__ __forceinline__ void cs_zero_sums(const CsDev& P, fe* lane_lds, uint32_t B) {
-  const uint32_t acc0 = 2 * P.width + P.n_temps;
-  for (uint32_t t = 0; t < P.D; ++t) lane_lds[(acc0 + t) * B] = fe_zero();
+  if (SUMS) {
+    cs_block_sum(la, B, lred, lin + blockIdx.x);
+    cs_block_sum(lb, B, lred, lin + gridDim.x + blockIdx.x);
+  }
 }
 
 template <bool SUMS>
@@ -177,12 +184,8 @@ __device__ __forceinline__ void cs_sums_body(const CsDev& P, const fe* __restric
     cs_accumulate(P, lane_lds, B, valid, dc, dd);
     __syncthreads();  // the next chunk's loads overwrite other lanes' slots
   }
-  cs_block_sums(P, lane_lds, B, partials);
-  if (SUMS) {
-    __shared__ fe lred[4];
-    cs_block_sum(la, B, lred, lin + blockIdx.x);
-    cs_block_sum(lb, B, lred, lin + gridDim.x + blockIdx.x);
-  }
+  __shared__ fe lred[4];
+  cs_write_sums<SUMS>(P, lane_lds, B, partials, la, lb, lred, lin);
 }
 
 // (the kernels without sum columns keep their argument lists)
@@ -239,12 +242,8 @@ __device__ __forceinline__ void cs_fold_sums_body(const CsDev& P, fe* m, fe* d, 
     cs_accumulate(P, lane_lds, B, valid, dc, dd);
     __syncthreads();
   }
-  cs_block_sums(P, lane_lds, B, partials);
-  if (SUMS) {
-    __shared__ fe lred[4];
-    cs_block_sum(la, B, lred, lin + blockIdx.x);
-    cs_block_sum(lb, B, lred, lin + gridDim.x + blockIdx.x);
-  }
+  __shared__ fe lred[4];
+  cs_write_sums<SUMS>(P, lane_lds, B, partials, la, lb, lred, lin);
 }
 
 __global__ void __launch_bounds__(256)
@@ -430,13 +429,16 @@ cs_round_lin_kernel(const fe* __restrict__ partials, uint32_t nb, uint32_t D,
 static inline size_t cs_lds_bytes(const CsDev& P, uint32_t threads) {
   return (size_t)(2 * P.width + P.n_temps + P.D) * threads * sizeof(fe);
 }
+// what the sums and the fold + sums launches both need
+static inline bool cs_launch_ok(const CsDev& P, uint32_t threads, uint32_t smask, const fe* lin) {
+  return threads >= 64 && threads <= 256 && !(threads & 63) && P.D <= kCsMaxD && (!smask || lin) &&
+         cs_lds_bytes(P, threads) <= kCsLdsBytes;
+}
 
 hipError_t launch_cs_sums(const CsDev& P, uint32_t threads, const fe* m, const fe* d, uint64_t h,
                           fe* partials, hipStream_t st, uint32_t* nb, uint32_t smask, fe* lin) {
+  if (!cs_launch_ok(P, threads, smask, lin) || h == 0) return hipErrorInvalidValue;
   const size_t lds = cs_lds_bytes(P, threads);
-  if (threads < 64 || threads > 256 || (threads & 63) || lds > kCsLdsBytes || P.D > kCsMaxD || h == 0 ||
-      (smask && !lin))
-    return hipErrorInvalidValue;
   const uint32_t n = cs_blocks(h, threads);
   if (smask)
     hipLaunchKernelGGL(cs_sums_lin_kernel, dim3(n), dim3(threads), lds, st, P, m, d, h, partials,
@@ -450,10 +452,8 @@ hipError_t launch_cs_sums(const CsDev& P, uint32_t threads, const fe* m, const f
 hipError_t launch_cs_fold_sums(const CsDev& P, uint32_t threads, fe* m, fe* d, uint64_t S, fe r,
                                const fe* r_dev, fe* partials, hipStream_t st, uint32_t* nb,
                                uint32_t smask, fe* lin) {
+  if (!cs_launch_ok(P, threads, smask, lin) || S < 4) return hipErrorInvalidValue;
   const size_t lds = cs_lds_bytes(P, threads);
-  if (threads < 64 || threads > 256 || (threads & 63) || lds > kCsLdsBytes || P.D > kCsMaxD || S < 4 ||
-      (smask && !lin))
-    return hipErrorInvalidValue;
   const uint32_t n = cs_blocks(S / 4, threads);
   if (smask)
     hipLaunchKernelGGL(cs_fold_sums_lin_kernel, dim3(n), dim3(threads), lds, st, P, m, d, S, r, r_dev,

@@ -49,20 +49,17 @@ inline uint32_t tc_blocks(uint64_t height, uint32_t width) {
   return (uint32_t)(tiles < kTcMaxBlocks ? tiles : kTcMaxBlocks);
 }
 
-// out[j * height + i] = in[i * width + j], i < height = 2^log_height,
-// j < width (1..32); in and out must not overlap.
+// out[j * height + i] = in[i * width + col0 + j], i < height = 2^log_height,
+// j < ncols (col0 + ncols <= width, width 1..32); in and out must not overlap.
+// The tile, the pitch and the grid are those of an ncols-wide trace --
+// tc_tile_rows(ncols), tc_pitch(ncols, R), tc_blocks(height, ncols).  The pitch
+// rule above is a statement about the lane -> (i, j) map and the LDS slot
+// j * pitch + i alone; in the range kernel that map is (e / ncols, e mod ncols),
+// so the rule holds with ncols for W.  What changes with a range narrower than
+// the width is the global side only (runs of ncols * 16 bytes at a stride of
+// width * 16; the range kernel); the whole width runs trace_columns_kernel on
+// contiguous tiles.  Reads nothing outside the range.
 hipError_t launch_trace_columns(const fe* in, fe* out, uint32_t log_height, uint32_t width,
-                                hipStream_t st);
-
-// out[j * height + i] = in[i * width + col0 + j], i < height, j < ncols
-// (col0 + ncols <= width): the tile, the pitch and the grid are those of an
-// ncols-wide trace -- tc_tile_rows(ncols), tc_pitch(ncols, R), tc_blocks(height,
-// ncols).  The pitch rule above is a statement about the lane -> (i, j) map and
-// the LDS slot j * pitch + i alone; in the range kernel that map is (e / ncols,
-// e mod ncols), so the rule holds with ncols for W.  What changes with the
-// range is the global side only (runs of ncols * 16 bytes at a stride of
-// width * 16).  Reads nothing outside the range.
-hipError_t launch_trace_columns_range(const fe* in, fe* out, uint32_t log_height, uint32_t width,
-                                      uint32_t col0, uint32_t ncols, hipStream_t st);
+                                uint32_t col0, uint32_t ncols, hipStream_t st);
 
 }  // namespace mlh

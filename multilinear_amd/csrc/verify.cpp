@@ -16,6 +16,7 @@
 #include "host_field.hpp"
 #include "host_sha256.hpp"
 #include "host_transcript.hpp"
+#include "system_head.hpp"
 
 using namespace mlh;
 
@@ -402,6 +403,13 @@ static u128 horner(const std::vector<u128>& c, u128 x) {
   return acc;
 }
 
+// The number of constraint challenges: next_power_of_two().trailing_zeros() (system.rs:83-87)
+static uint32_t cs_log_nc(uint32_t n_constraints) {
+  uint32_t log_nc = 0;
+  while ((1ull << log_nc) < n_constraints) ++log_nc;
+  return log_nc;
+}
+
 extern "C" {
 
 mlh_status mlh_cs_program_create(const uint8_t* bytes, uint64_t len, mlh_cs_program** out) {
@@ -447,8 +455,7 @@ mlh_status mlh_cs_launch_info(const mlh_cs_program* prog, uint32_t log_height, u
 mlh_status mlh_system_challenges(mlh_transcript* tr, uint32_t log_rows, uint32_t n_randoms,
                                  uint32_t n_constraints, uint8_t* row_out, uint8_t* trace_out,
                                  uint8_t* constraint_out, uint8_t* mask_out) {
-  uint32_t log_nc = 0;  // next_power_of_two().trailing_zeros() (system.rs:83-87)
-  while ((1ull << log_nc) < n_constraints) ++log_nc;
+  const uint32_t log_nc = cs_log_nc(n_constraints);
   if (!tr || log_rows > 64 || (log_rows && !row_out) || (n_randoms && !trace_out) ||
       (log_nc && !constraint_out) || (n_constraints && !mask_out))
     return MLH_ERR_INVALID;
@@ -479,6 +486,30 @@ mlh_status mlh_system_trace_randoms(const mlh_transcript* tr, const uint8_t root
 
 }  // extern "C"
 
+// The transcript head of every system proof (system_head.hpp; the order is
+// mlhip.h's): the one place where the provers and the verifiers derive it.
+mlh_status mlh::system_head(mlh_transcript* tr, const CsProgram& P, uint32_t log_height,
+                            const uint8_t root1[32], const uint8_t* root2, uint32_t sum_column_mask,
+                            const uint8_t sum[16], const uint8_t* column_sum, SystemHead* out) {
+  if (!tr || !root1 || !sum || !out || (sum_column_mask && !column_sum)) return MLH_ERR_INVALID;
+  std::vector<uint8_t> cons(16ull * cs_log_nc(P.n_constraints));
+  mlh_transcript_absorb(tr, root1, 32);  // 1.
+  uint8_t c[16];
+  mlh_transcript_next_challenge(tr, c);  // 2. vec![next_challenge(); n] (system.rs:139)
+  for (uint32_t i = 0; i < P.n_randoms; ++i) memcpy(out->randoms.data() + 16ull * i, c, 16);
+  if (root2) mlh_transcript_absorb(tr, root2, 32);  // 3.
+  const mlh_status st = mlh_system_challenges(tr, log_height, 0, P.n_constraints, out->row.data(),
+                                              nullptr, cons.data(), out->mask.data());  // 4.
+  if (st != MLH_OK) return st;
+  memcpy(out->claim, sum, 16);
+  if (sum_column_mask) {  // 5.
+    mlh_transcript_absorb(tr, column_sum, 16);
+    mlh_transcript_next_challenge(tr, out->beta);
+    h_store(out->claim, h_add(h_load(sum), h_mul(h_load(out->beta), h_load(column_sum))));
+  }
+  return MLH_OK;
+}
+
 // System::verify_with_evaluations (sumcheck.rs:91-124); rs_out (optional)
 // receives the challenges it derives.
 // smask / beta: the sum columns' term (mlh_cs_sumcheck_verify_sums); sum is
@@ -502,7 +533,7 @@ static mlh_status cs_sumcheck_verify_rs(const mlh_cs_program* prog, uint32_t log
     return MLH_ERR_INVALID;
   if (!load_canonical(host_output, P.width, output) || !load_canonical(polys, L * D, co))
     return MLH_ERR_VERIFY;
-  const mlh::HostSha256 saved = tr->sha;
+  TranscriptGuard guard(tr);
   const u128 inv2 = h_inv(2);
   std::vector<u128> rs, pol(D + 1);
   u128 claim = h_load(sum), r = 0;
@@ -530,11 +561,39 @@ static mlh_status cs_sumcheck_verify_rs(const mlh_cs_program* prog, uint32_t log
       if ((smask >> j) & 1u) lin = h_add(lin, output[j]);
     lin = h_mul(lin, h_load(beta));
   }
-  if (h_add(h_mul(delta, comp), lin) != claim) {  // :119-123
-    tr->sha = saved;
-    return MLH_ERR_VERIFY;
-  }
+  if (h_add(h_mul(delta, comp), lin) != claim) return MLH_ERR_VERIFY;  // :119-123
+  guard.keep();
   if (rs_out) *rs_out = rs;
+  return MLH_OK;
+}
+
+// What follows the header checks of both system verifiers: the head, the
+// sumcheck against the claimed output, then the opening(s) at its rs -- pcs1 for
+// the first pcs1->fri.num_codes columns, pcs2 (null: one phase) for the rest.
+// Every rejection is MLH_ERR_VERIFY with the transcript as at entry.
+static mlh_status system_verify_core(const mlh_cs_program* prog, uint32_t L, uint32_t sum_column_mask,
+                                     const uint8_t sum[16], const uint8_t* column_sum,
+                                     const uint8_t* polys, const uint8_t* output,
+                                     const mlh_batched_pcs_proof* pcs1,
+                                     const mlh_batched_pcs_proof* pcs2, mlh_transcript* tr) {
+  TranscriptGuard guard(tr);
+  SystemHead h(prog->p, L);
+  std::vector<u128> rs;
+  mlh_status st = system_head(tr, prog->p, L, pcs1->fri.batch_commitment,
+                              pcs2 ? pcs2->fri.batch_commitment : nullptr, sum_column_mask, sum,
+                              column_sum, &h);
+  if (st == MLH_OK)
+    st = cs_sumcheck_verify_rs(prog, L, h.row.data(), h.randoms.data(), h.mask.data(),
+                               sum_column_mask, h.beta, h.claim, polys, output, tr, &rs);
+  if (st == MLH_OK) {
+    std::vector<uint8_t> in(16ull * L);
+    for (uint32_t i = 0; i < L; ++i) h_store(in.data() + 16ull * i, rs[i]);
+    st = mlh_batched_pcs_verify(pcs1, L, in.data(), output, tr);
+    if (st == MLH_OK && pcs2)
+      st = mlh_batched_pcs_verify(pcs2, L, in.data(), output + 16ull * pcs1->fri.num_codes, tr);
+  }
+  if (st != MLH_OK) return MLH_ERR_VERIFY;
+  guard.keep();
   return MLH_OK;
 }
 
@@ -569,31 +628,8 @@ mlh_status mlh_system_verify(const mlh_cs_program* prog, uint32_t log_height, co
       proof->width != P.width || proof->degree != P.degree || proof->pcs.fri.num_codes != P.width ||
       h_load(sum) >= kModulus)
     return MLH_ERR_VERIFY;
-  const uint32_t L = log_height;
-  const mlh::HostSha256 saved = tr->sha;
-  // 1. the commitment; 2. the challenges (system.rs:39-54)
-  mlh_transcript_absorb(tr, proof->pcs.fri.batch_commitment, 32);
-  uint32_t log_nc = 0;
-  while ((1ull << log_nc) < P.n_constraints) ++log_nc;
-  std::vector<uint8_t> row(16ull * L), rnd(16ull * P.n_randoms + 16), cons(16ull * log_nc + 16),
-      mask(16ull * P.n_constraints);
-  mlh_status st = mlh_system_challenges(tr, L, P.n_randoms, P.n_constraints, row.data(), rnd.data(),
-                                        cons.data(), mask.data());
-  // 3. the sumcheck against the claimed output; 4. the opening at its rs
-  std::vector<u128> rs;
-  if (st == MLH_OK)
-    st = cs_sumcheck_verify_rs(prog, L, row.data(), rnd.data(), mask.data(), 0, nullptr, sum,
-                               proof->sumcheck_polys, proof->output, tr, &rs);
-  if (st == MLH_OK) {
-    std::vector<uint8_t> in(16ull * L);
-    for (uint32_t i = 0; i < L; ++i) h_store(in.data() + 16ull * i, rs[i]);
-    st = mlh_batched_pcs_verify(&proof->pcs, L, in.data(), proof->output, tr);
-  }
-  if (st != MLH_OK) {
-    tr->sha = saved;
-    return MLH_ERR_VERIFY;
-  }
-  return MLH_OK;
+  return system_verify_core(prog, log_height, 0, sum, nullptr, proof->sumcheck_polys, proof->output,
+                            &proof->pcs, nullptr, tr);
 }
 
 mlh_status mlh_system_verify_phased(const mlh_cs_program* prog, uint32_t log_height,
@@ -612,46 +648,8 @@ mlh_status mlh_system_verify_phased(const mlh_cs_program* prog, uint32_t log_hei
       (P1 < W && (!proof->pcs[1].sumcheck_polys || proof->pcs[1].fri.num_codes != W - P1)) ||
       h_load(sum) >= kModulus || h_load(column_sum) >= kModulus)
     return MLH_ERR_VERIFY;
-  const mlh::HostSha256 saved = tr->sha;
-  // 1. root 1; 2. the trace randoms; 3. root 2; 4. the other challenges and the mask
-  mlh_transcript_absorb(tr, proof->pcs[0].fri.batch_commitment, 32);
-  uint32_t log_nc = 0;
-  while ((1ull << log_nc) < P.n_constraints) ++log_nc;
-  std::vector<uint8_t> row(16ull * L), rnd(16ull * P.n_randoms + 16), cons(16ull * log_nc + 16),
-      mask(16ull * P.n_constraints);
-  {
-    uint8_t c[16];
-    mlh_transcript_next_challenge(tr, c);
-    for (uint32_t i = 0; i < P.n_randoms; ++i) memcpy(rnd.data() + 16ull * i, c, 16);
-  }
-  if (P1 < W) mlh_transcript_absorb(tr, proof->pcs[1].fri.batch_commitment, 32);
-  mlh_status st = mlh_system_challenges(tr, L, 0, P.n_constraints, row.data(), nullptr, cons.data(),
-                                        mask.data());
-  // 5. beta and the combined claim
-  uint8_t beta[16] = {0}, claim[16];
-  memcpy(claim, sum, 16);
-  if (sum_column_mask) {
-    mlh_transcript_absorb(tr, column_sum, 16);
-    mlh_transcript_next_challenge(tr, beta);
-    h_store(claim, h_add(h_load(sum), h_mul(h_load(beta), h_load(column_sum))));
-  }
-  // 6. the sumcheck against the claimed output; 7., 8. the openings at its rs
-  std::vector<u128> rs;
-  if (st == MLH_OK)
-    st = cs_sumcheck_verify_rs(prog, L, row.data(), rnd.data(), mask.data(), sum_column_mask, beta,
-                               claim, proof->sumcheck_polys, proof->output, tr, &rs);
-  if (st == MLH_OK) {
-    std::vector<uint8_t> in(16ull * L);
-    for (uint32_t i = 0; i < L; ++i) h_store(in.data() + 16ull * i, rs[i]);
-    st = mlh_batched_pcs_verify(&proof->pcs[0], L, in.data(), proof->output, tr);
-    if (st == MLH_OK && P1 < W)
-      st = mlh_batched_pcs_verify(&proof->pcs[1], L, in.data(), proof->output + 16ull * P1, tr);
-  }
-  if (st != MLH_OK) {
-    tr->sha = saved;
-    return MLH_ERR_VERIFY;
-  }
-  return MLH_OK;
+  return system_verify_core(prog, L, sum_column_mask, sum, column_sum, proof->sumcheck_polys,
+                            proof->output, &proof->pcs[0], P1 < W ? &proof->pcs[1] : nullptr, tr);
 }
 
 }  // extern "C"

@@ -25,11 +25,8 @@ import functools
 import cs_cases
 import cs_reference as R
 import system_reference as S
-from oracle import batched as OB
-from oracle import coracle as OC
 from oracle import field as F
 from oracle import transcript as OT
-from oracle.fri import query_index
 
 M = F.M
 
@@ -83,58 +80,6 @@ def sumcheck(sysm, ot, sum_columns, beta, claim):
     return pols, rs, tables.matrix[:sysm.columns]
 
 
-def _opening_bytes(tr, inputs, outputs, pcs):
-    """Replays an opening on `tr` (the state before it) and returns every byte
-    it absorbs, in order (batched_pcs.rs:186-250 as S._query_indices)."""
-    out = []
-
-    def absorb(b):
-        tr.absorb(b)
-        out.append(b)
-
-    for x in inputs:
-        absorb(F.to_bytes(x))
-    for y in outputs:
-        absorb(F.to_bytes(y))
-    for i, poly in enumerate(pcs["polys"]):
-        if i == 0:
-            absorb(pcs["batch_commitment"])
-            absorb(F.to_bytes(tr.next_challenge()))
-        else:
-            absorb(pcs["commitments"][i - 1])
-        for c in poly:
-            absorb(F.to_bytes(c))
-    absorb(F.to_bytes(pcs["last_elem"]))
-    domain = 1 << (len(pcs["commitments"]) + 1 + OB.LOG_BLOWUP)
-    for want in pcs["indices"]:
-        idx = query_index(tr, domain)
-        assert idx == want
-        absorb(idx.to_bytes(8, "little"))
-    assert tr.random() == pcs["last_random"]
-    return b"".join(out)
-
-
-def _open(ot, prefix, rs, outputs, columns, log_height):
-    """One BatchedPCSProof::prove on `ot` (advanced past it) -> (the proof's
-    parts, the prefix of whatever follows)."""
-    if log_height <= S.PY_MAX_LOG:
-        before = ot.clone()
-        pr = OB.BatchedPCSProof.prove(rs, outputs, columns, ot)
-        fp = pr.fri_proof
-        pcs = dict(batch_commitment=fp.batch_commitment, commitments=list(fp.commitments),
-                   polys=[tuple(p) for p in pr.sumcheck_polynomials], last_elem=fp.last_elem,
-                   last_random=fp.last_random, indices=S._query_indices(pr, before),
-                   queries=S._flat_queries(fp.queries))
-        return pcs, None
-    flat = [v for c in columns for v in c]
-    cp = OC.pcs_prove_par(S._limbs(flat), log_height, rs, outputs, batched=True, prefix=prefix)
-    assert cp["rc"] == 0
-    pcs = dict(batch_commitment=cp["batch_root"], commitments=cp["roots"], polys=cp["polys"],
-               last_elem=cp["last_elem"], last_random=cp["last_random"], indices=cp["indices"],
-               queries=cp["queries"])
-    return pcs, prefix + _opening_bytes(ot, rs, outputs, pcs)
-
-
 def prove(seed, fns, degree, width, randoms, log_height, matrix, pre, sum_columns, total=None,
           column_sum=None, matrix1=None):
     """-> dict: the proof's parts in host form and the transcript digests.
@@ -170,10 +115,10 @@ def prove(seed, fns, degree, width, randoms, log_height, matrix, pre, sum_column
     after_sumcheck = ot.random()
     coeff_bytes = b"".join(F.to_bytes(c) for p in pols for c in p)
     prefix += coeff_bytes
-    pcs1, prefix = _open(ot, prefix, rs, output[:P], columns1, log_height)        # 7
+    pcs1, prefix = S._open(ot, prefix, rs, output[:P], columns1, log_height)        # 7
     pcs = [pcs1]
     if P < W:
-        pcs2, prefix = _open(ot, prefix, rs, output[P:], columns[P:], log_height)  # 8
+        pcs2, prefix = S._open(ot, prefix, rs, output[P:], columns[P:], log_height)  # 8
         pcs.append(pcs2)
         assert pcs2["batch_commitment"] == root2
     assert pcs1["batch_commitment"] == root1
@@ -199,25 +144,6 @@ def model(name):
     return prove(c.seed, c.fns, c.degree, c.width, c.randoms, c.log_height, c.matrix(), P, sc)
 
 
-def _fill_pcs(holder, c_pcs, pcs):
-    """The model's opening into a multilinear_amd BatchedPCSProof's buffers
-    and the mlh_batched_pcs_proof struct `c_pcs` that points at them."""
-    fp = holder.fri_proof
-    assert len(pcs["queries"]) == fp.qbytes * OB.NUM_QUERIES
-    ctypes.memmove(fp._q, pcs["queries"], len(pcs["queries"]))
-    if pcs["commitments"]:
-        ctypes.memmove(fp._commit, b"".join(pcs["commitments"]), 32 * len(pcs["commitments"]))
-    raw = b"".join(F.to_bytes(a) + F.to_bytes(b) for a, b in pcs["polys"])
-    ctypes.memmove(holder._polys, raw, len(raw))
-    f = c_pcs.fri
-    f.num_trees = len(pcs["commitments"])
-    f.num_queries = OB.NUM_QUERIES
-    f.query_indices = None
-    f.batch_commitment[:] = list(pcs["batch_commitment"])
-    f.last_elem[:] = list(F.to_bytes(pcs["last_elem"]))
-    f.last_random[:] = list(pcs["last_random"])
-
-
 def pack(mo):
     """A model proof as mlh_phased_proof: a multilinear_amd PhasedSystemProof
     (the buffer holder) filled with the model's bytes."""
@@ -228,6 +154,6 @@ def pack(mo):
     out = b"".join(F.to_bytes(v) for v in mo["output"])
     ctypes.memmove(p._output, out, len(out))
     for i, pcs in enumerate(mo["pcs"]):
-        _fill_pcs(p.pcs[i], p.c.pcs[i], pcs)
+        S._fill_pcs(p.pcs[i], p.c.pcs[i], pcs)
     p._sync()
     return p

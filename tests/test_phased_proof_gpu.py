@@ -76,6 +76,20 @@ def test_range_transpose_is_the_slice(log_height, width, col0, ncols):
     assert torch.equal(out, out2)
 
 
+@pytest.mark.parametrize("log_height,width", [(5, 7), (11, 6)])
+def test_range_over_the_whole_width_is_trace_columns(log_height, width):
+    """col0 = 0, ncols = width runs the contiguous kernel: mlh_trace_columns'
+    bytes and launch shape.  (5, 7): one short tile; (11, 6): several tiles of
+    an odd-pitch width."""
+    m = D.random_device((1 << log_height) * width, seed=1000 * log_height + width)
+    out = CS.trace_columns(m, width, columns=(0, width))
+    assert torch.equal(out, CS.trace_columns(m, width))
+    rows, blocks = ctypes.c_uint32(), ctypes.c_uint32()
+    assert D.lib().mlh_trace_columns_launch_info(log_height, width, ctypes.byref(rows),
+                                                 ctypes.byref(blocks)) == 0
+    assert _range_info(log_height, width, 0, width) == (rows.value, blocks.value)
+
+
 def test_range_transpose_block_takes_a_second_tile():
     """The smallest shape at which a block loops: the grid caps at 1024 blocks
     and the tile has at least 64 rows (ncols = 31: 64 x 31 <= 2048 < 128 x 31),
