@@ -1,14 +1,20 @@
-// C ABI (include/mlhip.h) and the C++ host layer above the gfx950 kernels.
+// C ABI (include/mlhip.h) and the C++ host layer above the gfx950 kernels:
+// host orchestration only, no kernel lives here.
 //
-// This file mirrors the reference's prover-side orchestration:
-//   FriProverData::{init, fold_step, fold, open_query_at}  src/fri/mod.rs:57-175
-//   FriProof::{prove, verify, verify_queries}               src/fri/mod.rs:260-341
-//   SumcheckTables::compute_sumcheck_polynomial(s)          sumcheck.rs:77-202
-//   PCSProof::{prove, verify}                               multilinear_pcs.rs:90-190
-// with every large vector device resident; only roots (32 B), round sums
-// (32 B), the last element and the opened query paths cross PCIe.  The
-// Fiat-Shamir transcript runs on the host (it is a strict sequence of small
-// SHA-256 updates; one host round trip per round).
+// Here: the context, the pool and the twiddle-table cache, the NTT /
+// Reed-Solomon / Merkle / field entries, and the provers above FRI --
+//   SumcheckTables::compute_sumcheck_polynomial(s)   sumcheck.rs:77-202
+//   PCSProof::prove                                  multilinear_pcs.rs:90-136
+//   BatchedPCSProof::prove                           batched_pcs.rs:127-180
+// the trace commitment, the constraint-system sumcheck and the system proofs.
+// The FRI prover is fri_prover.hip; verifiers and host transcript, verify.cpp.
+// Every large vector is device resident; only roots, round sums (32 B each),
+// the last element and the opened query paths cross PCIe.  The whole-proof
+// entries run the Fiat-Shamir transcript on the device (FriDevLoop): the kernel
+// that writes a root or a round's sums draws the challenge, one sync ends the
+// commit phase, and the host transcript replays the absorbs and checks every
+// challenge (ReplayCheck).  Only the stepwise entries, whose challenges come
+// from the caller, run it on the host, one round trip per step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -32,12 +38,14 @@
 #include "context.hpp"
 #include "cs_program.hpp"
 #include "cs_sumcheck.hpp"
+#include "fri_prover.hpp"
 #include "fused_ntt.hpp"
 #include "merkle.hpp"
 #include "ntt.hpp"
 #include "sha256.hpp"
 #include "sumcheck.hpp"
 #include "system_head.hpp"
+#include "tables.hpp"
 #include "trace_commit.hpp"
 #include "transcript_dev.hpp"
 
@@ -47,8 +55,10 @@ using namespace mlh;
 // Table cache bound: when a new table would take the cache past its limit,
 // least-recently-used tables are freed (after the stream drains, since queued
 // kernels may still read them).  The tables one operation fetches are stamped
-// consecutively and fewer than kTablePin (an NTT of 2^40: 5 stage + 4 + 4
-// inter-pass tables; a PCS prove: those + 2 fold tables), so the newest
+// consecutively and fewer than kTablePin.  An NTT of kMaxPasses = 6 passes: 6
+// stage tables, 5 + 5 inter-pass tables (TA, TB) and pass 0's progression and
+// step tables, 18 at the most (13 for the default plan of 2^40).  A PCS prove:
+// those, the fold-layer table and the 2 fold tables, 21.  So the newest
 // kTablePin stamps -- every table the running operation holds a pointer to --
 // are never evicted.
 constexpr uint64_t kTablePin = 24;
@@ -185,11 +195,55 @@ static mlh_status get_ntt_tables(mlh_ctx* ctx, u128 gen, uint32_t log_n, bool in
 }
 
 // gen must have order exactly 2^log_n
-static bool check_generator(u128 gen, uint32_t log_n) {
+bool mlh::check_generator(u128 gen, uint32_t log_n) {
   if (gen >= kModulus) return false;
   if (log_n == 0) return gen == 1;
   const u128 half = h_pow(gen, (u128)1 << (log_n - 1));
   return half == kModulus - 1;  // gen^(N/2) = -1  <=>  order exactly N
+}
+
+// the root of a tree of `leaves` leaves: one synchronising D2H copy (out may be null)
+mlh_status mlh::read_root(mlh_ctx* ctx, const uint8_t* layers, uint64_t leaves, uint8_t out[32]) {
+  if (!out) return MLH_OK;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, layers + (2 * leaves - 2) * 32, 32,
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(out, ctx->pinned, 32);
+  return MLH_OK;
+}
+
+// Fold twiddles gen_pows[len - e] = g^(-e), e < len = 2^log_len (fri/mod.rs:106-110),
+// as T_lo[e mod 4096] * T_hi[e / 4096] of g^-1.
+mlh_status mlh::fold_tables_g(mlh_ctx* ctx, u128 g, uint32_t log_len, const fe** tlo,
+                              const fe** thi) {
+  const u128 ginv = h_inv(g);
+  MLH_TRY(get_table(ctx, ginv, 4096, 1, tlo));
+  MLH_TRY(get_table(ctx, h_pow(ginv, 4096), hi_count(log_len), 1, thi));
+  return MLH_OK;
+}
+static mlh_status fold_tables(mlh_ctx* ctx, uint32_t log_domain, const fe** tlo, const fe** thi) {
+  return fold_tables_g(ctx, h_pow2_generator(log_domain), log_domain, tlo, thi);
+}
+
+// Every fold layer's twiddles of the domain of g (order 2^L) in one cached
+// table (fri.hip fold_layer_table): a pair's twiddle is one 16-B load instead
+// of a product of two table entries.  Domains up to 2^25 (512 MiB, the size of
+// the reference's own gen_pows table there); *out = nullptr above that.
+#ifndef MLH_FOLD_TABLE_MAX_LOG
+#define MLH_FOLD_TABLE_MAX_LOG 25
+#endif
+mlh_status mlh::fold_layer_table(mlh_ctx* ctx, u128 g, uint32_t L, const fe** out) {
+  *out = nullptr;
+  if (L < 2 || L > MLH_FOLD_TABLE_MAX_LOG) return MLH_OK;
+  const TableKey key{h_inv(g), (1ull << L) - 1, 0, 2};
+  if (table_hit(ctx, key, out)) return MLH_OK;
+  fe* d = nullptr;
+  MLH_TRY(table_alloc(ctx, key, ((1ull << L) - 1) * sizeof(fe), &d));
+  const fe *tlo, *thi;  // (after the big allocation: it cannot evict these)
+  MLH_TRY(fold_tables_g(ctx, g, L, &tlo, &thi));
+  HIP_TRY(ctx, launch_fold_layer_table(d, tlo, thi, L, ctx->stream));
+  *out = d;
+  return MLH_OK;
 }
 
 static mlh_status ensure_ntt_scratch(mlh_ctx* ctx, uint32_t log_n) {
@@ -685,15 +739,6 @@ mlh_status mlh_reed_solomon_brev(mlh_ctx* ctx, const void* dev_coeffs, uint32_t 
 
 uint64_t mlh_merkle_layers_bytes(uint64_t leaves) { return leaves ? (2 * leaves - 1) * 32 : 0; }
 
-static mlh_status read_root(mlh_ctx* ctx, const uint8_t* layers, uint64_t leaves, uint8_t out[32]) {
-  if (!out) return MLH_OK;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, layers + (2 * leaves - 2) * 32, 32,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(out, ctx->pinned, 32);
-  return MLH_OK;
-}
-
 static bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 
 mlh_status mlh_merkle_commit_pairs(mlh_ctx* ctx, const void* dev_code, uint32_t log_code,
@@ -732,40 +777,6 @@ mlh_status mlh_merkle_batch_commit(mlh_ctx* ctx, const void* dev_items, uint64_t
   return read_root(ctx, layers, count, root_out);
 }
 
-// Fold twiddles gen_pows[len - e] = g^(-e), e < len = 2^log_len (fri/mod.rs:106-110),
-// as T_lo[e mod 4096] * T_hi[e / 4096] of g^-1.
-static mlh_status fold_tables_g(mlh_ctx* ctx, u128 g, uint32_t log_len, const fe** tlo,
-                                const fe** thi) {
-  const u128 ginv = h_inv(g);
-  MLH_TRY(get_table(ctx, ginv, 4096, 1, tlo));
-  MLH_TRY(get_table(ctx, h_pow(ginv, 4096), hi_count(log_len), 1, thi));
-  return MLH_OK;
-}
-static mlh_status fold_tables(mlh_ctx* ctx, uint32_t log_domain, const fe** tlo, const fe** thi) {
-  return fold_tables_g(ctx, h_pow2_generator(log_domain), log_domain, tlo, thi);
-}
-
-// Every fold layer's twiddles of the domain of g (order 2^L) in one cached
-// table (fri.hip fold_layer_table): a pair's twiddle is one 16-B load instead
-// of a product of two table entries.  Domains up to 2^25 (512 MiB, the size of
-// the reference's own gen_pows table there); *out = nullptr above that.
-#ifndef MLH_FOLD_TABLE_MAX_LOG
-#define MLH_FOLD_TABLE_MAX_LOG 25
-#endif
-static mlh_status fold_layer_table(mlh_ctx* ctx, u128 g, uint32_t L, const fe** out) {
-  *out = nullptr;
-  if (L < 2 || L > MLH_FOLD_TABLE_MAX_LOG) return MLH_OK;
-  const TableKey key{h_inv(g), (1ull << L) - 1, 0, 2};
-  if (table_hit(ctx, key, out)) return MLH_OK;
-  fe* d = nullptr;
-  MLH_TRY(table_alloc(ctx, key, ((1ull << L) - 1) * sizeof(fe), &d));
-  const fe *tlo, *thi;  // (after the big allocation: it cannot evict these)
-  MLH_TRY(fold_tables_g(ctx, g, L, &tlo, &thi));
-  HIP_TRY(ctx, launch_fold_layer_table(d, tlo, thi, L, ctx->stream));
-  *out = d;
-  return MLH_OK;
-}
-
 mlh_status mlh_fri_fold(mlh_ctx* ctx, const void* dev_layer, uint32_t log_layer, uint32_t k,
                         uint32_t log_domain, const uint8_t r[16], void* dev_next) {
   if (!ctx || !dev_layer || !dev_next || !r) return fail(ctx, MLH_ERR_INVALID, "null argument");
@@ -777,617 +788,6 @@ mlh_status mlh_fri_fold(mlh_ctx* ctx, const void* dev_layer, uint32_t log_layer,
                                reinterpret_cast<fe*>(dev_next), to_fe(h_load(r)), tlo, thi, k,
                                1ull << log_domain, ctx->stream));
   return MLH_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// FRI prover (FriProverData)
-// ---------------------------------------------------------------------------
-struct FriLayer {
-  const fe* values = nullptr;  // 2^log_n values (pairs i, i + n/2)
-  void* owned_values = nullptr;
-  uint8_t* tree = nullptr;  // 2L-1 digests, L = n/2
-  uint32_t log_n = 0;
-  uint8_t root[32];
-};
-
-struct mlh_fri_prover {
-  mlh_ctx* ctx;
-  uint32_t log_code;
-  // gen_pows of the reference's FriProverData calls (fri/mod.rs:58,79,136,261):
-  // a geometric table of 2^log_gp powers of gp_gen; fold twiddle
-  // gen_pows[len - i 2^k] = gp_gen^(-i 2^k).  Default: the code's domain.
-  u128 gp_gen = 0;
-  uint32_t log_gp = 0;
-  std::vector<FriLayer> layers;
-  bool has_last = false;
-  uint8_t last[16];
-  ~mlh_fri_prover() {
-    for (auto& l : layers) {
-      pool_free(ctx, l.owned_values);
-      pool_free(ctx, l.tree);
-    }
-  }
-};
-
-// gen_pows = [g^0 .. g^(2^log_gp - 1)] (NttField::pow_2_generator_powers,
-// ntt/mod.rs:18-28, or any generator of order exactly 2^log_gp).  The
-// reference indexes gen_pows[len - i 2^k] with i 2^k < 2^(log_code - 1), so a
-// table shorter than half the code underflows its index (a panic there).
-static mlh_status set_gen_pows(mlh_ctx* ctx, mlh_fri_prover* p, const uint8_t* gen,
-                               uint32_t log_gp) {
-  if (!gen) {
-    p->gp_gen = h_pow2_generator(p->log_code);
-    p->log_gp = p->log_code;
-    return MLH_OK;
-  }
-  if (log_gp > 40 || log_gp + 1 < p->log_code)
-    return fail(ctx, MLH_ERR_INVALID, "gen_pows shorter than half the code");
-  const u128 g = h_load(gen);
-  if (!check_generator(g, log_gp))
-    return fail(ctx, MLH_ERR_BAD_GENERATOR, "gen_pows[1] must have order exactly gen_pows.len()");
-  p->gp_gen = g;
-  p->log_gp = log_gp;
-  return MLH_OK;
-}
-
-extern "C" {
-
-mlh_status mlh_fri_prover_init(mlh_ctx* ctx, const void* dev_code, uint32_t log_code,
-                               mlh_transcript* tr, mlh_fri_prover** out) {
-  return mlh_fri_prover_init_gp(ctx, dev_code, log_code, nullptr, 0, tr, out);
-}
-
-mlh_status mlh_fri_prover_init_gp(mlh_ctx* ctx, const void* dev_code, uint32_t log_code,
-                                  const uint8_t gen_pows_1[16], uint32_t log_gen_pows,
-                                  mlh_transcript* tr, mlh_fri_prover** out) {
-  if (!ctx || !dev_code || !tr || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (log_code < 1 || log_code > 40)
-    return fail(ctx, MLH_ERR_NOT_POW2, "Input size must be a power of two");
-  std::unique_ptr<mlh_fri_prover> p(new mlh_fri_prover());
-  p->ctx = ctx;
-  p->log_code = log_code;
-  MLH_TRY(set_gen_pows(ctx, p.get(), gen_pows_1, log_gen_pows));
-  FriLayer l0;
-  l0.values = reinterpret_cast<const fe*>(dev_code);
-  l0.log_n = log_code;
-  const uint64_t L = 1ull << (log_code - 1);
-  void* tree;
-  MLH_TRY(pool_alloc(ctx, mlh_merkle_layers_bytes(L), &tree));
-  l0.tree = reinterpret_cast<uint8_t*>(tree);
-  p->layers.push_back(l0);
-  MLH_TRY(mlh_merkle_commit_pairs(ctx, dev_code, log_code, tree, p->layers[0].root));
-  mlh_transcript_absorb(tr, p->layers[0].root, 32);
-  *out = p.release();
-  return MLH_OK;
-}
-
-}  // extern "C"
-
-// fold_step (fri/mod.rs:79-134) with the table (gen, log_gp): twiddle
-// gen_pows[len - i 2^k] = gen^(-(i 2^k) mod len).  The reference accepts any k
-// whose indices stay in the table -- (n/2 - 1) 2^k <= len, else its usize index
-// underflows (a panic, MLH_ERR_INVALID here); its callers pass k in sequence.
-static mlh_status fold_step_impl(mlh_ctx* ctx, mlh_fri_prover* p, u128 gen, uint32_t log_gp,
-                                 uint32_t k, const uint8_t r[16], mlh_transcript* tr) {
-  // a batched prover's inner view has no tree before batched_fold_step, nor
-  // after a step that produced the last element directly (log_code 2); the
-  // reference panics on merkle_trees.last().unwrap() there
-  if (p->layers.empty())
-    return fail(ctx, MLH_ERR_INVALID, "fold_step before any tree (batched_fold_step not applied)");
-  const FriLayer& cur = p->layers.back();
-  const uint32_t log_n = cur.log_n;  // n = 2 * pairs
-  const uint64_t blowup = 1ull << MLH_LOG_BLOWUP;
-  if ((1ull << log_n) <= blowup) return MLH_OK;  // fri/mod.rs:83-85
-  // (after the last element, the reference folds its last tree again and
-  // re-absorbs the element: layers.back() is still that tree here, too)
-  const uint64_t half_n = 1ull << (log_n - 1);
-  // (log space first: half_n - 1 < 2^(log_n - 1), so with (log_n - 1) + k <= 62
-  // the shift cannot wrap 64 bits; beyond it the product exceeds any table)
-  if (k > 40 || (log_n - 1) + k > 62 || ((half_n - 1) << k) > (1ull << log_gp))
-    return fail(ctx, MLH_ERR_INVALID, "gen_pows index len - i*2^k underflows (fri/mod.rs:106-110)");
-  const fe *tlo, *thi;
-  MLH_TRY(fold_tables_g(ctx, gen, log_gp, &tlo, &thi));
-  const fe rr = to_fe(h_load(r));
-  FriLayer nx;
-  nx.log_n = log_n - 1;
-  PoolBuf vb(ctx), tb(ctx);  // released into the new layer on success only
-  MLH_TRY(vb.alloc(half_n * sizeof(fe)));
-  void* vals = vb.p;
-  nx.values = reinterpret_cast<const fe*>(vals);
-  if (half_n == blowup) {  // fri/mod.rs:116-126
-    HIP_TRY(ctx, launch_fri_fold(cur.values, 1ull << log_n, reinterpret_cast<fe*>(vals), rr, tlo,
-                                 thi, k, 1ull << log_gp, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, vals, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (memcmp(ctx->pinned, ctx->pinned + 16, 16) != 0)
-      return fail(ctx, MLH_ERR_NOT_RS_CODE, "not an RS code");
-    memcpy(p->last, ctx->pinned, 16);
-    p->has_last = true;
-    mlh_transcript_absorb(tr, p->last, 16);
-    return MLH_OK;
-  }
-  const uint64_t L = half_n / 2;
-  MLH_TRY(tb.alloc(mlh_merkle_layers_bytes(L)));
-  nx.tree = tb.as<uint8_t>();
-  HIP_TRY(ctx, launch_fri_fold_commit(cur.values, 1ull << log_n, reinterpret_cast<fe*>(vals),
-                                      nx.tree, rr, tlo, thi, k, 1ull << log_gp,
-                                      ctx->stream));
-  MLH_TRY(read_root(ctx, nx.tree, L, nx.root));
-  nx.owned_values = vb.release();
-  tb.release();
-  p->layers.push_back(nx);
-  mlh_transcript_absorb(tr, p->layers.back().root, 32);
-  return MLH_OK;
-}
-
-extern "C" {
-
-mlh_status mlh_fri_prover_fold_step(mlh_ctx* ctx, mlh_fri_prover* p, uint32_t k,
-                                    const uint8_t r[16], mlh_transcript* tr) {
-  if (!ctx || !p || !r || !tr) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  return fold_step_impl(ctx, p, p->gp_gen, p->log_gp, k, r, tr);
-}
-
-mlh_status mlh_fri_prover_fold_step_gp(mlh_ctx* ctx, mlh_fri_prover* p, const uint8_t gen_pows_1[16],
-                                       uint32_t log_gen_pows, uint32_t k, const uint8_t r[16],
-                                       mlh_transcript* tr) {
-  if (!ctx || !p || !gen_pows_1 || !r || !tr) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (log_gen_pows < 1 || log_gen_pows > 40) return fail(ctx, MLH_ERR_INVALID, "gen_pows length");
-  const u128 g = h_load(gen_pows_1);
-  if (!check_generator(g, log_gen_pows))
-    return fail(ctx, MLH_ERR_BAD_GENERATOR, "gen_pows[1] must have order exactly gen_pows.len()");
-  return fold_step_impl(ctx, p, g, log_gen_pows, k, r, tr);
-}
-
-}  // extern "C"
-
-// FriProverData::fold (fri/mod.rs:136-145) with the transcript on the device:
-// every round's challenge is derived on the GPU from the root just written,
-// so the whole commit phase is one stream of kernels with a single sync at
-// the end; the host transcript then replays the same absorbs (root_0,
-// root_1, ..., last element) and ends in the identical state.
-static_assert(sizeof(DevSha) == sizeof(HostSha256), "transcript layouts differ");
-
-// Device-side commit loop state: [transcript | r_0..r_steps | last (16) |
-// flag (16) | batch root (32) | fingerprint r (16) | roots 32 x (steps + 1) |
-// polys 32 x steps | prev (16) | extra (16 x n_extra)].
-struct FriDevLoop {
-  mlh_ctx* ctx;
-  mlh_fri_prover* p;
-  const fe *tlo = nullptr, *thi = nullptr;
-  const fe* twt = nullptr;  // every fold layer's twiddles (fold_layer_table), or nullptr
-  PoolBuf scratch;
-  size_t off_r = 128, off_last = 0, off_flag = 0, off_broot = 0, off_fr = 0, off_roots = 0,
-         off_polys = 0, off_prev = 0, off_extra = 0;
-  bool done = false;
-  // batched mode: the m codes ([m][N]) and the batch-layer tree
-  const fe* codes = nullptr;
-  uint32_t m = 0;
-  PoolBuf btree;
-  const uint8_t* bt = nullptr;  // the batch-layer tree: btree, or the caller's built one
-  explicit FriDevLoop(mlh_ctx* c, mlh_fri_prover* pr) : ctx(c), p(pr), scratch(c), btree(c) {}
-  uint8_t* sb() const { return scratch.as<uint8_t>(); }
-  DevSha* dt() const { return reinterpret_cast<DevSha*>(sb()); }
-  fe* r(uint32_t k) const { return reinterpret_cast<fe*>(sb() + off_r) + k; }
-  uint8_t* root(uint32_t t) const { return sb() + off_roots + 32 * t; }
-  fe* poly(uint32_t k) const { return reinterpret_cast<fe*>(sb() + off_polys) + 2 * k; }
-  fe* prev() const { return reinterpret_cast<fe*>(sb() + off_prev); }
-  fe* fr() const { return reinterpret_cast<fe*>(sb() + off_fr); }
-  fe* extra() const { return reinterpret_cast<fe*>(sb() + off_extra); }
-
-  mlh_status layout(uint32_t log_code, const mlh_transcript* tr, size_t n_extra = 0) {
-    const uint32_t steps = log_code - MLH_LOG_BLOWUP;
-    off_last = off_r + 16 * (steps + 1);
-    off_flag = off_last + 16;
-    off_broot = off_flag + 16;
-    off_fr = off_broot + 32;
-    off_roots = off_fr + 16;
-    off_polys = off_roots + 32 * (steps + 1);
-    off_prev = off_polys + 32 * steps;
-    off_extra = off_prev + 16;
-    MLH_TRY(scratch.alloc(off_extra + 16 * (n_extra ? n_extra : 1)));
-    if (!p->log_gp) {
-      p->gp_gen = h_pow2_generator(log_code);
-      p->log_gp = log_code;
-    }
-    if (p->log_gp == log_code) MLH_TRY(fold_layer_table(ctx, p->gp_gen, log_code, &twt));
-    MLH_TRY(fold_tables_g(ctx, p->gp_gen, p->log_gp, &tlo, &thi));
-    memcpy(ctx->pinned, &tr->sha, sizeof(DevSha));
-    HIP_TRY(ctx, hipMemcpyAsync(dt(), ctx->pinned, sizeof(DevSha), hipMemcpyHostToDevice,
-                                ctx->stream));
-    return MLH_OK;
-  }
-
-  // BatchedFriProverData::init (batched_fri.rs:41-98): batch layer over the
-  // m codes' RS pairs, absorb its root, fingerprint_r = next_challenge(),
-  // absorb LE16(fingerprint_r); r_0 = next_challenge() if challenge_r0.
-  // built_tree (optional): the batch layer's tree over these codes, already
-  // built (a trace commitment's); only its root is absorbed then.
-  mlh_status init_batched(const fe* dev_codes, uint32_t num_codes, uint32_t log_code,
-                          const mlh_transcript* tr, bool challenge_r0, size_t n_extra = 0,
-                          const uint8_t* built_tree = nullptr) {
-    MLH_TRY(layout(log_code, tr, n_extra));
-    codes = dev_codes;
-    m = num_codes;
-    const uint64_t N = 1ull << log_code, L = N / 2;
-    if (built_tree) {
-      bt = built_tree;
-      HIP_TRY(ctx, launch_transcript_absorb(dt(), bt + (2 * L - 2) * 32, 32, fr(), ctx->stream,
-                                            sb() + off_broot));
-    } else {
-      MLH_TRY(btree.alloc(mlh_merkle_layers_bytes(L)));
-      uint8_t* t = btree.as<uint8_t>();
-      bt = t;
-      HIP_TRY(ctx, launch_batch_pairs_leaves(codes, m, N, t, ctx->stream));
-      HIP_TRY(ctx, launch_merkle_levels(t, L, ctx->stream, RootAbsorb{dt(), fr(), sb() + off_broot}));
-    }
-    HIP_TRY(ctx, launch_transcript_absorb(dt(), reinterpret_cast<const uint8_t*>(fr()), 16,
-                                          challenge_r0 ? r(0) : nullptr, ctx->stream));
-    return MLH_OK;
-  }
-
-  // batched_fold_step (batched_fri.rs:100-176): fold the fingerprinted pairs
-  // with r at rp into the inner prover's first layer (or the last element).
-  mlh_status step_batched(const fe* rp, bool challenge_next, const fe* poly_next = nullptr) {
-    const uint32_t L = p->log_code;
-    const uint64_t N = 1ull << L, half_n = N / 2;
-    void* vals;
-    MLH_TRY(pool_alloc(ctx, half_n * sizeof(fe), &vals));
-    if (half_n == (1ull << MLH_LOG_BLOWUP)) {
-      HIP_TRY(ctx, launch_batched_fold_leaves(codes, m, N, fr(), rp, tlo, thi,
-                                              reinterpret_cast<fe*>(vals), nullptr, ctx->stream));
-      HIP_TRY(ctx, launch_fri_last(reinterpret_cast<const fe*>(vals), dt(),
-                                   reinterpret_cast<uint32_t*>(sb() + off_flag),
-                                   reinterpret_cast<fe*>(sb() + off_last), ctx->stream));
-      pool_free(ctx, vals);
-      done = true;
-      return MLH_OK;
-    }
-    FriLayer nx;
-    nx.log_n = L - 1;
-    nx.owned_values = vals;
-    nx.values = reinterpret_cast<const fe*>(vals);
-    const uint64_t leaves = half_n / 2;
-    void* tree;
-    MLH_TRY(pool_alloc(ctx, mlh_merkle_layers_bytes(leaves), &tree));
-    nx.tree = reinterpret_cast<uint8_t*>(tree);
-    p->layers.push_back(nx);
-    HIP_TRY(ctx, launch_batched_fold_leaves(codes, m, N, fr(), rp, tlo, thi,
-                                            reinterpret_cast<fe*>(vals), nx.tree, ctx->stream));
-    HIP_TRY(ctx, launch_merkle_levels(nx.tree, leaves, ctx->stream,
-                                      RootAbsorb{dt(), challenge_next ? r(1) : nullptr, root(0), poly_next}));
-    return MLH_OK;
-  }
-
-  // poly0 (optional): 32 bytes absorbed after root 0, before its challenge;
-  // n_extra: 16-byte slots at extra()
-  mlh_status init(const void* dev_code, uint32_t log_code, const mlh_transcript* tr,
-                  bool challenge_after_root0, const fe* poly0 = nullptr, size_t n_extra = 0) {
-    MLH_TRY(layout(log_code, tr, n_extra));
-    return init_after_layout(dev_code, log_code, challenge_after_root0, poly0);
-  }
-  // init's commit of layer 0, after layout() (whose extra() slots the caller
-  // may fill first)
-  mlh_status init_after_layout(const void* dev_code, uint32_t log_code, bool challenge_after_root0,
-                               const fe* poly0) {
-    FriLayer l0;
-    l0.values = reinterpret_cast<const fe*>(dev_code);
-    l0.log_n = log_code;
-    const uint64_t L = 1ull << (log_code - 1);
-    void* tree;
-    MLH_TRY(pool_alloc(ctx, mlh_merkle_layers_bytes(L), &tree));
-    l0.tree = reinterpret_cast<uint8_t*>(tree);
-    p->layers.push_back(l0);
-    HIP_TRY(ctx, launch_commit_pairs(
-                     l0.values, L, l0.tree, ctx->stream,
-                     RootAbsorb{dt(), challenge_after_root0 ? r(0) : nullptr, root(0), poly0}));
-    return MLH_OK;
-  }
-
-  // fold_step k with the challenge at rp (device); absorbs the new root (or
-  // the last element) and (poly_next) 32 more bytes; writes next_challenge()
-  // to r(k + 1) if challenge_next.
-  // job (optional): a PCS round run by an extra workgroup of the fold launch
-  mlh_status step(uint32_t k, const fe* rp, bool challenge_next, const fe* poly_next = nullptr,
-                  const PcsJob* job = nullptr) {
-    if (done) return MLH_OK;
-    const FriLayer cur = p->layers.back();
-    const uint32_t log_n = cur.log_n;
-    if ((1ull << log_n) <= (1ull << MLH_LOG_BLOWUP)) return MLH_OK;
-    const uint64_t half_n = 1ull << (log_n - 1);
-    void* vals;
-    MLH_TRY(pool_alloc(ctx, half_n * sizeof(fe), &vals));
-    if (half_n == (1ull << MLH_LOG_BLOWUP)) {  // fri/mod.rs:116-126
-      if (job || poly_next) {
-        pool_free(ctx, vals);
-        return fail(ctx, MLH_ERR_INVALID, "no PCS round after the last FRI fold");
-      }
-      HIP_TRY(ctx, launch_fri_fold(cur.values, 1ull << log_n, reinterpret_cast<fe*>(vals), fe{},
-                                   tlo, thi, k, 1ull << p->log_gp, ctx->stream, ShardMap(), rp));
-      HIP_TRY(ctx, launch_fri_last(reinterpret_cast<const fe*>(vals), dt(),
-                                   reinterpret_cast<uint32_t*>(sb() + off_flag),
-                                   reinterpret_cast<fe*>(sb() + off_last), ctx->stream));
-      pool_free(ctx, vals);
-      done = true;
-      return MLH_OK;
-    }
-    FriLayer nx;
-    nx.log_n = log_n - 1;
-    nx.owned_values = vals;
-    nx.values = reinterpret_cast<const fe*>(vals);
-    const uint64_t L = half_n / 2;
-    void* tree;
-    MLH_TRY(pool_alloc(ctx, mlh_merkle_layers_bytes(L), &tree));
-    nx.tree = reinterpret_cast<uint8_t*>(tree);
-    p->layers.push_back(nx);
-    const uint32_t t = (uint32_t)p->layers.size() - 1;
-    const uint32_t Lg = p->log_gp;  // the layer table's part for fold k (pairs of a 2^(Lg - k) layer)
-    const fe* twl = twt && log_n + k == Lg ? twt + ((1ull << Lg) - (1ull << (Lg - k))) : nullptr;
-    HIP_TRY(ctx, launch_fri_fold_commit(
-                     cur.values, 1ull << log_n, reinterpret_cast<fe*>(vals), nx.tree, fe{}, tlo,
-                     thi, k, 1ull << p->log_gp, ctx->stream, ShardMap(), rp,
-                     RootAbsorb{dt(), challenge_next ? r(k + 1) : nullptr, root(t), poly_next}, job,
-                     twl));
-    return MLH_OK;
-  }
-
-  // one sync: challenges, last element, RS flag, roots (+ polys_bytes of
-  // sumcheck polys); then the cooperative kernels' failure word
-  mlh_status finish(size_t polys_bytes) {
-    if (!done) return fail(ctx, MLH_ERR_INVALID, "fold produced no last element");
-    const size_t nt = p->layers.size();
-    const size_t bytes = off_polys - off_r + polys_bytes;
-    if (bytes > kPinStage) return fail(ctx, MLH_ERR_INVALID, "proof staging too large");
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, sb() + off_r, bytes, hipMemcpyDeviceToHost,
-                                ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    MLH_TRY(device_check(ctx));
-    const uint8_t* h = ctx->pinned;
-    for (size_t t = 0; t < nt; ++t)
-      memcpy(p->layers[t].root, h + (off_roots - off_r) + 32 * t, 32);
-    uint32_t flag;
-    memcpy(&flag, h + (off_flag - off_r), 4);
-    if (flag) return fail(ctx, MLH_ERR_NOT_RS_CODE, "not an RS code");
-    memcpy(p->last, h + (off_last - off_r), 16);
-    p->has_last = true;
-    return MLH_OK;
-  }
-  // the device's challenge slot k, as copied back by finish()
-  const uint8_t* host_r(uint32_t k) const { return ctx->pinned + 16 * k; }
-  const uint8_t* host_polys() const { return ctx->pinned + (off_polys - off_r); }
-  const uint8_t* host_broot() const { return ctx->pinned + (off_broot - off_r); }
-  const uint8_t* host_fr() const { return ctx->pinned + (off_fr - off_r); }
-};
-
-// FriProverData::fold (fri/mod.rs:136-145) with the transcript on the device:
-// every round's challenge is derived on the GPU from the root just written,
-// so the whole commit phase is one stream of kernels with a single sync at
-// the end; the host transcript then replays the same absorbs (root_0,
-// root_1, ..., last element) and ends in the identical state.
-static mlh_status fri_fold_device(mlh_ctx* ctx, const void* dev_code, uint32_t log_code,
-                                  const uint8_t* gen, uint32_t log_gp, mlh_transcript* tr,
-                                  mlh_fri_prover** out) {
-  if (!ctx || !dev_code || !tr || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (log_code < 2 || log_code > 40)
-    return fail(ctx, log_code < 2 ? MLH_ERR_INVALID : MLH_ERR_NOT_POW2,
-                "fold needs 4 <= code length <= 2^40");
-  std::unique_ptr<mlh_fri_prover> p(new mlh_fri_prover());
-  p->ctx = ctx;
-  p->log_code = log_code;
-  MLH_TRY(set_gen_pows(ctx, p.get(), gen, log_gp));
-  FriDevLoop lp(ctx, p.get());
-  device_arm(ctx);
-  MLH_TRY(lp.init(dev_code, log_code, tr, true));
-  const uint32_t steps = log_code - MLH_LOG_BLOWUP;
-  for (uint32_t k = 0; k < steps; ++k) MLH_TRY(lp.step(k, lp.r(k), true));
-  MLH_TRY(lp.finish(0));
-  // host replay: root_t, then the challenge r_t the device drew from it
-  ReplayCheck rc(ctx, tr);
-  for (size_t t = 0; t < p->layers.size(); ++t) {
-    rc.absorb(p->layers[t].root, 32);
-    rc.expect(lp.host_r((uint32_t)t));
-  }
-  rc.absorb(p->last, 16);
-  MLH_TRY(rc.status());
-  *out = p.release();
-  return MLH_OK;
-}
-
-extern "C" {
-
-mlh_status mlh_fri_prover_fold(mlh_ctx* ctx, const void* dev_code, uint32_t log_code,
-                               mlh_transcript* tr, mlh_fri_prover** out) {
-  return fri_fold_device(ctx, dev_code, log_code, nullptr, 0, tr, out);
-}
-
-mlh_status mlh_fri_prover_fold_gp(mlh_ctx* ctx, const void* dev_code, uint32_t log_code,
-                                  const uint8_t gen_pows_1[16], uint32_t log_gen_pows,
-                                  mlh_transcript* tr, mlh_fri_prover** out) {
-  if (!gen_pows_1) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  return fri_fold_device(ctx, dev_code, log_code, gen_pows_1, log_gen_pows, tr, out);
-}
-
-uint32_t mlh_fri_prover_num_trees(const mlh_fri_prover* p) {
-  return p ? (uint32_t)p->layers.size() : 0;
-}
-
-mlh_status mlh_fri_prover_roots(const mlh_fri_prover* p, uint8_t* roots_out) {
-  if (!p || !roots_out) return MLH_ERR_INVALID;
-  for (size_t i = 0; i < p->layers.size(); ++i) memcpy(roots_out + 32 * i, p->layers[i].root, 32);
-  return MLH_OK;
-}
-
-mlh_status mlh_fri_prover_last_element(const mlh_fri_prover* p, uint8_t out[16]) {
-  if (!p || !out || !p->has_last) return MLH_ERR_INVALID;
-  memcpy(out, p->last, 16);
-  return MLH_OK;
-}
-
-void mlh_fri_prover_destroy(mlh_fri_prover* p) { delete p; }
-
-}  // extern "C"
-
-// Gather opened query records from the device-resident layers/trees.
-struct QueryTree {
-  const fe* values;
-  const uint8_t* tree;
-  uint32_t log_n;  // layer values
-};
-// The layer table travels in the kernel arguments (up to 40 layers, ~1 KB)
-// with, for a proof's 128 queries, the indices (1 KB): the query phase is then
-// one launch and one D2H copy, no host-to-device copies.
-constexpr uint32_t kMaxQueryTrees = 40;
-struct QueryTrees {
-  QueryTree t[kMaxQueryTrees];
-  uint32_t n;
-};
-static_assert(MLH_NUM_QUERIES == 128, "QueryIdx holds 128 indices");
-static_assert(sizeof(QueryTrees) + sizeof(mlh::QueryIdx) + 64 <= 4096, "kernel argument budget");
-
-// d_idx: device indices (openings of more than 128 queries), else idx.v
-__global__ void gather_queries_kernel(const QueryTrees trees, const mlh::QueryIdx idx,
-                                      const uint64_t* __restrict__ d_idx, uint32_t nq,
-                                      uint64_t qbytes, uint64_t base, uint8_t* __restrict__ out) {
-  const uint32_t q = blockIdx.x;
-  if (q >= nq) return;
-  const uint64_t iq = d_idx ? d_idx[q] : idx.v[q];
-  // record offsets per tree
-  uint64_t off = base;
-  for (uint32_t t = 0; t < trees.n; ++t) {
-    const QueryTree T = trees.t[t];
-    const uint64_t half = 1ull << (T.log_n - 1);  // leaves
-    const uint64_t i = iq % half;                   // fri/mod.rs:169-170
-    const uint32_t depth = T.log_n - 1;
-    uint8_t* rec = out + q * qbytes + off;
-    if (threadIdx.x == 0) {
-      fe_store(reinterpret_cast<fe*>(rec), fe_load(T.values + i));
-      fe_store(reinterpret_cast<fe*>(rec + 16), fe_load(T.values + i + half));
-    }
-    // siblings: level l node (i >> l) ^ 1, level l starts at sum_{j<l} half>>j
-    for (uint32_t l = threadIdx.x; l < depth; l += blockDim.x) {
-      const uint64_t lvl_off = 2 * half - (2 * half >> l);
-      const uint64_t sib = ((i >> l) ^ 1ull);
-      const uint4* src = reinterpret_cast<const uint4*>(T.tree + (lvl_off + sib) * 32);
-      uint4* dst = reinterpret_cast<uint4*>(rec + 32 + (uint64_t)l * 32);
-      dst[0] = src[0];
-      dst[1] = src[1];
-    }
-    off += 32ull * (1 + depth);
-  }
-}
-
-// Pinned host staging for a query phase: the gather kernels write the
-// records straight into it (zero-copy over PCIe, ~1.3 MB for a 2^25 code: no
-// device buffer, no copy launch), and it holds indices beyond 128.  Grow-only;
-// a caller's stream sync ends every use before the next one.  Allocated
-// non-coherent (explicitly; what flags 0 gives under the default
-// HIP_HOST_COHERENT=0): the kernels' writes become visible to the host only
-// at the end of the kernel, so EVERY host read of records a kernel wrote here
-// must follow a sync of the stream that ran it (each caller syncs ctx->stream
-// before copying records out).
-static mlh_status query_stage(mlh_ctx* ctx, size_t bytes, uint8_t** out) {
-  if (bytes > ctx->qstage_bytes) {
-    if (ctx->qstage) HIP_TRY(ctx, hipHostFree(ctx->qstage));
-    ctx->qstage = nullptr;
-    ctx->qstage_bytes = 0;
-    void* h = nullptr;
-    HIP_TRY(ctx, hipHostMalloc(&h, bytes, hipHostMallocNonCoherent));
-    ctx->qstage = reinterpret_cast<uint8_t*>(h);
-    ctx->qstage_bytes = bytes;
-  }
-  *out = ctx->qstage;
-  return MLH_OK;
-}
-
-// Launch the per-tree gathers of p's layers into records at d_out (qbytes
-// each, this part starting at byte `base` of a record; device or pinned host
-// memory); indices in idx.v, or
-// at d_idx (device) when nq > 128.
-static mlh_status gather_queries_dev(mlh_ctx* ctx, const mlh_fri_prover* p, const mlh::QueryIdx& idx,
-                                     const uint64_t* d_idx, uint32_t nq, uint64_t qbytes,
-                                     uint64_t base, uint8_t* d_out) {
-  const uint32_t nt = (uint32_t)p->layers.size();
-  if (nt == 0 || nq == 0) return MLH_OK;
-  if (nt > kMaxQueryTrees) return fail(ctx, MLH_ERR_INVALID, "more than 40 FRI layers");
-  if (nq > MLH_NUM_QUERIES && !d_idx) return fail(ctx, MLH_ERR_INVALID, "query indices not on the device");
-  QueryTrees qt;
-  qt.n = nt;
-  for (uint32_t t = 0; t < nt; ++t)
-    qt.t[t] = QueryTree{p->layers[t].values, p->layers[t].tree, p->layers[t].log_n};
-  hipLaunchKernelGGL(gather_queries_kernel, dim3(nq), dim3(64), 0, ctx->stream, qt, idx,
-                     nq > MLH_NUM_QUERIES ? d_idx : nullptr, nq, qbytes, base, d_out);
-  HIP_TRY(ctx, hipGetLastError());
-  return MLH_OK;
-}
-
-static mlh_status gather_queries(mlh_ctx* ctx, const mlh_fri_prover* p, const uint64_t* idx,
-                                 uint32_t nq, uint8_t* host_out) {
-  const uint64_t qbytes = mlh_fri_query_bytes(p->log_code);
-  const size_t off_out = nq > MLH_NUM_QUERIES ? 8ull * nq : 0;
-  uint8_t* h;
-  MLH_TRY(query_stage(ctx, off_out + nq * qbytes, &h));
-  mlh::QueryIdx qi;
-  memset(&qi, 0, sizeof(qi));
-  PoolBuf didx(ctx);
-  if (nq > MLH_NUM_QUERIES) {
-    memcpy(h, idx, 8ull * nq);
-    MLH_TRY(didx.alloc(nq * sizeof(uint64_t)));
-    HIP_TRY(ctx, hipMemcpyAsync(didx.p, h, nq * sizeof(uint64_t), hipMemcpyHostToDevice,
-                                ctx->stream));
-  } else {
-    memcpy(qi.v, idx, 8ull * nq);
-  }
-  MLH_TRY(gather_queries_dev(ctx, p, qi, didx.as<uint64_t>(), nq, qbytes, 0, h + off_out));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(host_out, h + off_out, nq * qbytes);
-  return MLH_OK;
-}
-
-// FriProof::prove tail (fri/mod.rs:266-284): query indices from the
-// transcript, openings, last_random.
-static mlh_status fri_queries(mlh_ctx* ctx, mlh_fri_prover* p, mlh_transcript* tr,
-                              mlh_fri_proof* proof) {
-  const uint64_t domain = 1ull << p->log_code;
-  proof->log_code = p->log_code;
-  proof->num_trees = (uint32_t)p->layers.size();
-  proof->num_queries = MLH_NUM_QUERIES;
-  std::vector<uint64_t> idx(MLH_NUM_QUERIES);
-  for (int q = 0; q < MLH_NUM_QUERIES; ++q) {
-    uint8_t rnd[32];
-    mlh_transcript_random(tr, rnd);
-    uint64_t u;
-    memcpy(&u, rnd, 8);
-    idx[q] = u % (domain / 2);
-    uint8_t le[8];
-    memcpy(le, &idx[q], 8);
-    mlh_transcript_absorb(tr, le, 8);
-  }
-  if (proof->query_indices) memcpy(proof->query_indices, idx.data(), idx.size() * 8);
-  if (proof->commitments) mlh_fri_prover_roots(p, proof->commitments);
-  memcpy(proof->last_elem, p->last, 16);
-  mlh_transcript_random(tr, proof->last_random);
-  if (proof->queries) MLH_TRY(gather_queries(ctx, p, idx.data(), MLH_NUM_QUERIES, proof->queries));
-  return MLH_OK;
-}
-
-extern "C" {
-
-mlh_status mlh_fri_prover_open_query(mlh_ctx* ctx, const mlh_fri_prover* p, uint64_t index,
-                                     uint8_t* out) {
-  if (!ctx || !p || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (index >= (1ull << (p->log_code - 1))) return fail(ctx, MLH_ERR_INVALID, "index out of bounds");
-  return gather_queries(ctx, p, &index, 1, out);
-}
-
-mlh_status mlh_fri_prover_open_queries(mlh_ctx* ctx, const mlh_fri_prover* p,
-                                       const uint64_t* idx, uint32_t nq, uint8_t* out) {
-  if (!ctx || !p || !idx || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  for (uint32_t q = 0; q < nq; ++q)
-    if (idx[q] >= (1ull << (p->log_code - 1))) return fail(ctx, MLH_ERR_INVALID, "index out of bounds");
-  if (nq == 0) return MLH_OK;
-  return gather_queries(ctx, p, idx, nq, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1490,28 +890,6 @@ mlh_status mlh_merkle_open_pairs(mlh_ctx* ctx, const void* dev_values, uint32_t 
   HIP_TRY(ctx, hipMemcpyAsync(out, dout.p, nq * rec, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MLH_OK;
-}
-
-mlh_status mlh_fri_prove(mlh_ctx* ctx, const void* dev_code, uint32_t log_code, mlh_transcript* tr,
-                         mlh_fri_proof* proof) {
-  if (!ctx || !dev_code || !tr || !proof) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  mlh_fri_prover* p = nullptr;
-  MLH_TRY(mlh_fri_prover_fold(ctx, dev_code, log_code, tr, &p));
-  mlh_status s = fri_queries(ctx, p, tr, proof);
-  mlh_fri_prover_destroy(p);
-  return s;
-}
-
-mlh_status mlh_fri_prove_gp(mlh_ctx* ctx, const void* dev_code, uint32_t log_code,
-                            const uint8_t gen_pows_1[16], uint32_t log_gen_pows, mlh_transcript* tr,
-                            mlh_fri_proof* proof) {
-  if (!ctx || !dev_code || !tr || !proof || !gen_pows_1)
-    return fail(ctx, MLH_ERR_INVALID, "null argument");
-  mlh_fri_prover* p = nullptr;
-  MLH_TRY(mlh_fri_prover_fold_gp(ctx, dev_code, log_code, gen_pows_1, log_gen_pows, tr, &p));
-  mlh_status s = fri_queries(ctx, p, tr, proof);
-  mlh_fri_prover_destroy(p);
-  return s;
 }
 
 // ---------------------------------------------------------------------------
@@ -2060,7 +1438,7 @@ static mlh_status pcs_rounds_fused(mlh_ctx* ctx, FriDevLoop& lp, const fe* evals
   PcsRounds pr(ctx, lp);
   MLH_TRY(pr.init(evals, work, n, host_inputs, output, nullptr));
   // FRI init: root 0 | (c1, c2)_0 -> r_0
-  MLH_TRY(lp.init_after_layout(code, log_domain, true, lp.poly(0)));
+  MLH_TRY(lp.init(code, log_domain, true, lp.poly(0)));
   for (uint32_t k = 0; k < n; ++k) {
     const uint32_t kn = k + 1;  // the round whose polynomial follows r_k
     PcsJob job{};
@@ -2093,16 +1471,15 @@ mlh_status mlh_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t n_vars,
   // PCSProverData::init (:28-42) + fold loop (:57-75), transcript on the
   // device: per round the sumcheck round kernel absorbs (c1, c2) and derives
   // r, which the sumcheck fold and the FRI fold_step read from HBM.
-  std::unique_ptr<mlh_fri_prover> fp(new mlh_fri_prover());
-  fp->ctx = ctx;
-  fp->log_code = log_domain;
-  FriDevLoop lp(ctx, fp.get());
+  mlh_fri_prover fp(ctx, log_domain);
+  FriDevLoop lp(ctx, &fp);
   device_arm(ctx);
   if (n_vars <= ctx->pcs_fused_max) {
     MLH_TRY(pcs_rounds_fused(ctx, lp, reinterpret_cast<const fe*>(dev_evals), matrix.as<fe>(),
                              n_vars, host_inputs, output, code.p, log_domain, tr));
   } else {
-    MLH_TRY(lp.init(code.p, log_domain, tr, false));
+    MLH_TRY(lp.layout(log_domain, tr));
+    MLH_TRY(lp.init(code.p, log_domain, false));
     EqSumcheck es(ctx);  // delta = eq(inputs), factored (build_tables_for_pcs)
     MLH_TRY(es.init(reinterpret_cast<const fe*>(dev_evals), matrix.as<fe>(), n_vars, host_inputs));
     memcpy(ctx->pinned + kPinSlotA, output, 16);
@@ -2121,20 +1498,18 @@ mlh_status mlh_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t n_vars,
   const uint8_t* polys = lp.host_polys();
   if (proof->sumcheck_polys) memcpy(proof->sumcheck_polys, polys, 32ull * n_vars);
   ReplayCheck rc(ctx, tr);
-  rc.absorb(fp->layers[0].root, 32);
+  rc.absorb(fp.layers[0].root, 32);
   for (uint32_t k = 0; k < n_vars; ++k) {
     rc.absorb(polys + 32 * k, 16);
     rc.absorb(polys + 32 * k + 16, 16);
     rc.expect(lp.host_r(k));
-    if (k + 1 < fp->layers.size())
-      rc.absorb(fp->layers[k + 1].root, 32);
+    if (k + 1 < fp.layers.size())
+      rc.absorb(fp.layers[k + 1].root, 32);
     else
-      rc.absorb(fp->last, 16);
+      rc.absorb(fp.last, 16);
   }
   MLH_TRY(rc.status());
-  mlh_fri_prover* fpp = fp.get();
-  MLH_TRY(fri_queries(ctx, fpp, tr, &proof->fri));
-  return MLH_OK;
+  return fri_queries(ctx, &fp, tr, &proof->fri);
 }
 
 }  // extern "C"
@@ -2221,241 +1596,8 @@ mlh_status mlh_bench_ntt(mlh_ctx* ctx, void* dev_buf, uint32_t log_n, uint32_t i
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
-// batched FRI / batched PCS (src/fri/batched_fri.rs, batched_pcs.rs)
+// batched PCS (batched_pcs.rs; the batched FRI under it: fri_prover.hip)
 // ---------------------------------------------------------------------------
-// Queries of a batched proof (batched_fri.rs:287-300): the transcript draws
-// the indices, the batch column + batch siblings and the inner paths are
-// gathered into one device buffer, one D2H.
-static mlh_status batched_queries(mlh_ctx* ctx, FriDevLoop& lp, mlh_transcript* tr,
-                                  mlh_batched_fri_proof* pf) {
-  const uint32_t L = lp.p->log_code, m = lp.m;
-  const uint64_t N = 1ull << L;
-  std::vector<uint64_t> idx(MLH_NUM_QUERIES);
-  for (int q = 0; q < MLH_NUM_QUERIES; ++q) {
-    idx[q] = transcript_query_index(tr, N / 2);
-    uint8_t le[8];
-    memcpy(le, &idx[q], 8);
-    mlh_transcript_absorb(tr, le, 8);
-  }
-  pf->log_code = L;
-  pf->num_codes = m;
-  pf->num_trees = (uint32_t)lp.p->layers.size();
-  pf->num_queries = MLH_NUM_QUERIES;
-  if (pf->query_indices) memcpy(pf->query_indices, idx.data(), idx.size() * 8);
-  memcpy(pf->last_elem, lp.p->last, 16);
-  mlh_transcript_random(tr, pf->last_random);
-  if (pf->commitments) mlh_fri_prover_roots(lp.p, pf->commitments);
-  if (!pf->queries) return MLH_OK;
-  const uint64_t qbytes = mlh_batched_fri_query_bytes(L, m);
-  uint8_t* h;
-  MLH_TRY(query_stage(ctx, MLH_NUM_QUERIES * qbytes, &h));
-  mlh::QueryIdx qi;
-  memcpy(qi.v, idx.data(), 8ull * MLH_NUM_QUERIES);
-  HIP_TRY(ctx, launch_batch_queries(lp.codes, m, N, lp.bt, qi, MLH_NUM_QUERIES,
-                                    qbytes, h, ctx->stream));
-  MLH_TRY(gather_queries_dev(ctx, lp.p, qi, nullptr, MLH_NUM_QUERIES, qbytes,
-                             32ull * m + 32ull * (L - 1), h));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(pf->queries, h, MLH_NUM_QUERIES * qbytes);
-  return MLH_OK;
-}
-
-extern "C" {
-
-mlh_status mlh_batched_fri_prove(mlh_ctx* ctx, const void* dev_codes, uint32_t num_codes,
-                                 uint32_t log_code, mlh_transcript* tr,
-                                 mlh_batched_fri_proof* proof) {
-  if (!ctx || !dev_codes || !tr || !proof) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (num_codes == 0) return fail(ctx, MLH_ERR_INVALID, "Codes must not be empty");
-  if (log_code < 2 || log_code > 40)
-    return fail(ctx, MLH_ERR_NOT_POW2, "Code size must be a power of two (>= 4)");
-  std::unique_ptr<mlh_fri_prover> p(new mlh_fri_prover());
-  p->ctx = ctx;
-  p->log_code = log_code;
-  FriDevLoop lp(ctx, p.get());
-  device_arm(ctx);
-  MLH_TRY(lp.init_batched(reinterpret_cast<const fe*>(dev_codes), num_codes, log_code, tr, true));
-  // fold (batched_fri.rs:178-205): the batched step, then ordinary steps
-  MLH_TRY(lp.step_batched(lp.r(0), true));
-  const uint32_t steps = log_code - MLH_LOG_BLOWUP;
-  for (uint32_t k = 1; k < steps; ++k) MLH_TRY(lp.step(k, lp.r(k), true));
-  MLH_TRY(lp.finish(0));
-  // host transcript replay: batch root, fingerprint_r, inner roots, last
-  ReplayCheck rc(ctx, tr);
-  rc.absorb(lp.host_broot(), 32);
-  rc.expect(lp.host_fr());
-  rc.absorb(lp.host_fr(), 16);
-  rc.expect(lp.host_r(0));
-  for (size_t t = 0; t < p->layers.size(); ++t) {
-    rc.absorb(p->layers[t].root, 32);
-    rc.expect(lp.host_r((uint32_t)t + 1));
-  }
-  rc.absorb(p->last, 16);
-  MLH_TRY(rc.status());
-  memcpy(proof->batch_commitment, lp.host_broot(), 32);
-  return batched_queries(ctx, lp, tr, proof);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// BatchedFriProverData step by step (batched_fri.rs:9-224), host transcript:
-// init -> batched_fold_step(gen_pows, r, tr) -> the inner fri_data's
-// fold_step(gen_pows, k, r, tr) for k >= 1 (mlh_fri_prover_fold_step(_gp) on
-// the handle mlh_batched_fri_prover_inner returns) -> open_query_at.  The
-// whole-proof path (mlh_batched_fri_prove) keeps the transcript on the device.
-// ---------------------------------------------------------------------------
-struct mlh_batched_fri_prover {
-  mlh_ctx* ctx;
-  const fe* codes = nullptr;  // caller's [m][N], must outlive the prover
-  uint32_t m = 0, log_code = 0;
-  void* btree = nullptr;      // batch layer: N/2 leaves + levels
-  void* scal = nullptr;       // device [fingerprint_r | r]
-  uint8_t broot[32];
-  uint8_t fr[16];
-  mlh_fri_prover inner;       // fri_data: merkle_trees start at the folded layer
-  ~mlh_batched_fri_prover() {
-    pool_free(ctx, btree);
-    pool_free(ctx, scal);
-  }
-};
-
-extern "C" {
-
-mlh_status mlh_batched_fri_prover_init(mlh_ctx* ctx, const void* dev_codes, uint32_t num_codes,
-                                       uint32_t log_code, mlh_transcript* tr, mlh_batched_fri_prover** out) {
-  if (!ctx || !dev_codes || !tr || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (num_codes == 0) return fail(ctx, MLH_ERR_INVALID, "Codes must not be empty");
-  if (log_code < 2 || log_code > 40)
-    return fail(ctx, MLH_ERR_NOT_POW2, "Code size must be a power of two (>= 4)");
-  std::unique_ptr<mlh_batched_fri_prover> bp(new mlh_batched_fri_prover());
-  bp->ctx = ctx;
-  bp->codes = reinterpret_cast<const fe*>(dev_codes);
-  bp->m = num_codes;
-  bp->log_code = log_code;
-  bp->inner.ctx = ctx;
-  bp->inner.log_code = log_code - 1;  // its first tree is the folded layer's
-  bp->inner.gp_gen = h_pow2_generator(log_code);  // the batched code's domain
-  bp->inner.log_gp = log_code;
-  const uint64_t N = 1ull << log_code, L = N / 2;
-  MLH_TRY(pool_alloc(ctx, mlh_merkle_layers_bytes(L), &bp->btree));
-  MLH_TRY(pool_alloc(ctx, 32, &bp->scal));
-  uint8_t* bt = reinterpret_cast<uint8_t*>(bp->btree);
-  HIP_TRY(ctx, launch_batch_pairs_leaves(bp->codes, num_codes, N, bt, ctx->stream));
-  HIP_TRY(ctx, launch_merkle_levels(bt, L, ctx->stream));
-  MLH_TRY(read_root(ctx, bt, L, bp->broot));
-  // batched_fri.rs:82-89: absorb the root, fingerprint_r = next_challenge(),
-  // absorb LE16(fingerprint_r)
-  mlh_transcript_absorb(tr, bp->broot, 32);
-  mlh_transcript_next_challenge(tr, bp->fr);
-  mlh_transcript_absorb(tr, bp->fr, 16);
-  *out = bp.release();
-  return MLH_OK;
-}
-
-mlh_status mlh_batched_fri_prover_fold_step_gp(mlh_ctx* ctx, mlh_batched_fri_prover* bp,
-                                               const uint8_t gen_pows_1[16], uint32_t log_gen_pows,
-                                               const uint8_t r[16], mlh_transcript* tr) {
-  if (!ctx || !bp || !gen_pows_1 || !r || !tr) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (log_gen_pows < 1 || log_gen_pows > 40) return fail(ctx, MLH_ERR_INVALID, "gen_pows length");
-  const u128 g = h_load(gen_pows_1);
-  if (!check_generator(g, log_gen_pows))
-    return fail(ctx, MLH_ERR_BAD_GENERATOR, "gen_pows[1] must have order exactly gen_pows.len()");
-  const uint64_t N = 1ull << bp->log_code, half_n = N / 2;
-  if (N <= (1ull << MLH_LOG_BLOWUP)) return MLH_OK;  // batched_fri.rs:104-106
-  if (half_n - 1 > (1ull << log_gen_pows))
-    return fail(ctx, MLH_ERR_INVALID, "gen_pows index len - i underflows (batched_fri.rs:131-136)");
-  // (called again, the reference folds the batch layer again and pushes a
-  // second tree onto fri_data; this binding folds it once)
-  if (!bp->inner.layers.empty() || bp->inner.has_last)
-    return fail(ctx, MLH_ERR_INVALID, "batched_fold_step already applied");
-  const fe *tlo, *thi;
-  MLH_TRY(fold_tables_g(ctx, g, log_gen_pows, &tlo, &thi));
-  memcpy(ctx->pinned, bp->fr, 16);
-  memcpy(ctx->pinned + 16, r, 16);
-  fe* sc = reinterpret_cast<fe*>(bp->scal);
-  HIP_TRY(ctx, hipMemcpyAsync(sc, ctx->pinned, 32, hipMemcpyHostToDevice, ctx->stream));
-  PoolBuf vb(ctx), tb(ctx);  // released into fri_data on success only
-  MLH_TRY(vb.alloc(half_n * sizeof(fe)));
-  void* vals = vb.p;
-  if (half_n == (1ull << MLH_LOG_BLOWUP)) {  // batched_fri.rs:152-162
-    HIP_TRY(ctx, launch_batched_fold_leaves(bp->codes, bp->m, N, sc, sc + 1, tlo, thi,
-                                            reinterpret_cast<fe*>(vals), nullptr, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, vals, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (memcmp(ctx->pinned, ctx->pinned + 16, 16) != 0)
-      return fail(ctx, MLH_ERR_NOT_RS_CODE, "not an RS code");
-    memcpy(bp->inner.last, ctx->pinned, 16);
-    bp->inner.has_last = true;
-    mlh_transcript_absorb(tr, bp->inner.last, 16);
-    return MLH_OK;
-  }
-  FriLayer nx;
-  nx.log_n = bp->log_code - 1;
-  nx.values = reinterpret_cast<const fe*>(vals);
-  const uint64_t leaves = half_n / 2;
-  MLH_TRY(tb.alloc(mlh_merkle_layers_bytes(leaves)));
-  nx.tree = tb.as<uint8_t>();
-  HIP_TRY(ctx, launch_batched_fold_leaves(bp->codes, bp->m, N, sc, sc + 1, tlo, thi,
-                                          reinterpret_cast<fe*>(vals), nx.tree, ctx->stream));
-  HIP_TRY(ctx, launch_merkle_levels(nx.tree, leaves, ctx->stream));
-  MLH_TRY(read_root(ctx, nx.tree, leaves, nx.root));
-  nx.owned_values = vb.release();  // owned by fri_data from here on (its destructor frees them)
-  tb.release();
-  bp->inner.layers.push_back(nx);
-  mlh_transcript_absorb(tr, bp->inner.layers.back().root, 32);
-  return MLH_OK;
-}
-
-mlh_fri_prover* mlh_batched_fri_prover_inner(mlh_batched_fri_prover* bp) {
-  return bp ? &bp->inner : nullptr;
-}
-
-mlh_status mlh_batched_fri_prover_batch_root(const mlh_batched_fri_prover* bp, uint8_t out[32]) {
-  if (!bp || !out) return MLH_ERR_INVALID;
-  memcpy(out, bp->broot, 32);
-  return MLH_OK;
-}
-
-mlh_status mlh_batched_fri_prover_fingerprint_r(const mlh_batched_fri_prover* bp, uint8_t out[16]) {
-  if (!bp || !out) return MLH_ERR_INVALID;
-  memcpy(out, bp->fr, 16);
-  return MLH_OK;
-}
-
-mlh_status mlh_batched_fri_prover_open_query(mlh_ctx* ctx, const mlh_batched_fri_prover* bp,
-                                             uint64_t index, uint8_t* out) {
-  if (!ctx || !bp || !out) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  const uint32_t L = bp->log_code;
-  if (index >= (1ull << (L - 1))) return fail(ctx, MLH_ERR_INVALID, "index out of bounds");
-  const uint64_t qbytes = mlh_batched_fri_query_bytes(L, bp->m);
-  uint8_t* h;
-  MLH_TRY(query_stage(ctx, qbytes, &h));
-  mlh::QueryIdx qi;
-  memset(&qi, 0, sizeof(qi));
-  qi.v[0] = index;
-  HIP_TRY(ctx, launch_batch_queries(bp->codes, bp->m, 1ull << L, reinterpret_cast<const uint8_t*>(bp->btree),
-                                    qi, 1, qbytes, h, ctx->stream));
-  // the inner paths at index mod N/4 (batched_fri.rs:215-221; the gather
-  // reduces the index per tree); zero where the inner prover has fewer trees
-  const uint64_t base = 32ull * bp->m + 32ull * (L - 1);
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memset(h + base, 0, qbytes - base);
-  MLH_TRY(gather_queries_dev(ctx, &bp->inner, qi, nullptr, 1, qbytes, base, h));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(out, h, qbytes);
-  return MLH_OK;
-}
-
-void mlh_batched_fri_prover_destroy(mlh_batched_fri_prover* bp) {
-  if (bp) {
-    (void)hipStreamSynchronize(bp->ctx->stream);
-    delete bp;
-  }
-}
-
-}  // extern "C"
-
 // The transcript-independent front of BatchedPCSProof::prove
 // (batched_pcs.rs:135-149): per polynomial to_coefficient, bit reverse and
 // reed_solomon at blow-up 2, into dev_codes ([num_polys][2^(n_vars+1)]).
@@ -2495,10 +1637,8 @@ static mlh_status batched_pcs_open(mlh_ctx* ctx, const fe* dev_codes, const void
   ReplayCheck rc(ctx, tr);
   for (uint32_t i = 0; i < n_vars; ++i) rc.absorb(inputs + 16 * i, 16);
   for (uint32_t j = 0; j < num_polys; ++j) rc.absorb(outputs + 16 * j, 16);
-  std::unique_ptr<mlh_fri_prover> fp(new mlh_fri_prover());
-  fp->ctx = ctx;
-  fp->log_code = log_domain;
-  FriDevLoop lp(ctx, fp.get());
+  mlh_fri_prover fp(ctx, log_domain);
+  FriDevLoop lp(ctx, &fp);
   device_arm(ctx);
   const bool fused = n_vars <= ctx->pcs_fused_max;
   MLH_TRY(lp.init_batched(dev_codes, num_polys, log_domain, tr, false, fused ? 5 : 0, built_tree));
@@ -2556,10 +1696,10 @@ static mlh_status batched_pcs_open(mlh_ctx* ctx, const fe* dev_codes, const void
     rc.absorb(polys + 32 * k, 16);
     rc.absorb(polys + 32 * k + 16, 16);
     rc.expect(lp.host_r(k));
-    if (k < fp->layers.size())
-      rc.absorb(fp->layers[k].root, 32);
+    if (k < fp.layers.size())
+      rc.absorb(fp.layers[k].root, 32);
     else
-      rc.absorb(fp->last, 16);
+      rc.absorb(fp.last, 16);
   }
   MLH_TRY(rc.status());
   memcpy(proof->fri.batch_commitment, lp.host_broot(), 32);
@@ -2659,8 +1799,7 @@ static mlh_status trace_commit_impl(mlh_ctx* ctx, const void* dev_matrix, uint32
   MLH_TRY(batched_pcs_codes(ctx, c->evals, ncols, log_height, codes));
   // the batch layer of BatchedFriProverData::init (batched_fri.rs:41-81)
   uint8_t* bt = reinterpret_cast<uint8_t*>(c->tree);
-  HIP_TRY(ctx, launch_batch_pairs_leaves(codes, ncols, 2 * n, bt, ctx->stream));
-  HIP_TRY(ctx, launch_merkle_levels(bt, n, ctx->stream));
+  MLH_TRY(batch_layer_commit(ctx, codes, ncols, 2 * n, bt));
   MLH_TRY(read_root(ctx, bt, n, c->root));
   *out = c.release();
   return MLH_OK;

@@ -20,3 +20,15 @@ static inline uint64_t transcript_query_index(const mlh_transcript* tr, uint64_t
   memcpy(&u, rnd, 8);
   return u % half;
 }
+
+// The query phase's draws (fri/mod.rs:266-277): n indices modulo half, each
+// absorbed as its 8 LE bytes before the next one is drawn.
+static inline void transcript_draw_indices(mlh_transcript* tr, uint64_t half, uint32_t n,
+                                           uint64_t* idx) {
+  for (uint32_t q = 0; q < n; ++q) {
+    idx[q] = transcript_query_index(tr, half);
+    uint8_t le[8];
+    memcpy(le, &idx[q], 8);
+    tr->sha.update(le, 8);
+  }
+}

@@ -745,12 +745,7 @@ mlh_status mlh_sharded_fri_prove(mlh_ctx* ctx, const mlh_transport* t, const voi
   // queries (fri/mod.rs:266-277): the owner opens, records combined by a gather
   const uint64_t half = 1ull << (log_code - 1);
   std::vector<uint64_t> idx(MLH_NUM_QUERIES);
-  for (uint32_t q = 0; q < MLH_NUM_QUERIES; ++q) {
-    idx[q] = transcript_query_index(tr, half);
-    uint8_t le[8];
-    memcpy(le, &idx[q], 8);
-    mlh_transcript_absorb(tr, le, 8);
-  }
+  transcript_draw_indices(tr, half, MLH_NUM_QUERIES, idx.data());
   const uint64_t qbytes = mlh_fri_query_bytes(log_code);
   std::vector<uint8_t> mine(qbytes * MLH_NUM_QUERIES, 0);
   uint64_t layer_off = 0;

@@ -167,10 +167,8 @@ static mlh_status fri_verify_queries(const mlh_fri_proof* pf, mlh_transcript* tr
   const uint64_t qbytes = mlh_fri_query_bytes(L);
   const u128 last = h_load(pf->last_elem);
   for (uint32_t q = 0; q < pf->num_queries; ++q) {
-    const uint64_t index = transcript_query_index(tr, domain / 2);
-    uint8_t le[8];
-    memcpy(le, &index, 8);
-    mlh_transcript_absorb(tr, le, 8);
+    uint64_t index;
+    transcript_draw_indices(tr, domain / 2, 1, &index);
     if (pf->query_indices && pf->query_indices[q] != index) return MLH_ERR_VERIFY;
     if (!query_chain(pf->queries + q * qbytes, pf->commitments, pf->num_trees, domain / 2, index,
                      gen, rs.data(), last))
@@ -190,7 +188,8 @@ static mlh_status batched_verify_queries(const mlh_batched_fri_proof* pf, mlh_tr
   const uint64_t qbytes = mlh_batched_fri_query_bytes(L, m);
   const u128 inv2 = h_inv(2), last = h_load(pf->last_elem);
   for (uint32_t q = 0; q < pf->num_queries; ++q) {
-    const uint64_t index = transcript_query_index(tr, n);
+    uint64_t index;  // (drawn and absorbed; nothing below reads the transcript)
+    transcript_draw_indices(tr, n, 1, &index);
     if (pf->query_indices && pf->query_indices[q] != index) return MLH_ERR_VERIFY;
     const uint8_t* rec = pf->queries + q * qbytes;
     if (!verify_path_len(rec, 32ull * m, rec + 32ull * m, L - 1, pf->batch_commitment, index))
@@ -215,9 +214,6 @@ static mlh_status batched_verify_queries(const mlh_batched_fri_proof* pf, mlh_tr
                        rs.data() + 1, last))
         return MLH_ERR_VERIFY;
     }
-    uint8_t le[8];
-    memcpy(le, &index, 8);
-    mlh_transcript_absorb(tr, le, 8);
   }
   uint8_t lr[32];
   mlh_transcript_random(tr, lr);

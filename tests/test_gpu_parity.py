@@ -1188,6 +1188,80 @@ def test_batched_inner_fold_step_without_tree_rejected():
             assert fd.fold_roots()[:len(before)] == before and len(fd.fold_roots()) == len(before) + 1
 
 
+@pytest.mark.parametrize("m,log_code", [(2, 2), (2, 6)])
+def test_batched_fri_not_rs_code(m, log_code):
+    """The batch layer's last-pair check on the device transcript: random
+    non-codewords fail BatchedFriProof.prove with MLH_ERR_NOT_RS_CODE -- at
+    log_code 2 in the batched step itself (it produces the last element), at
+    log_code 6 in an ordinary step after it -- the caller's transcript is left
+    untouched, and the context proves real codes bit-exactly afterwards."""
+    from multilinear_amd.batched import BatchedFriProof
+    from oracle import batched as OB
+
+    n = 1 << log_code
+    tr = Transcript()
+    tr.absorb(b"batched not-RS")
+    before = tr.random()
+    with pytest.raises(_lib.MlhError) as e:
+        BatchedFriProof.prove(dev(rand_vals(m * n, 70 + log_code)), m, tr)
+    assert e.value.status == _lib.MLH_ERR_NOT_RS_CODE
+    assert tr.random() == before
+    gp = F.pow_2_generator_powers(log_code)
+    codes = [OF.reed_solomon([F.from_i64(7 * i + 3 + 100 * j) for i in range(n // 2)], gp[1])
+             for j in range(m)]
+    want = OB.BatchedFriProof.prove(codes, gp, OT.Transcript())
+    got = BatchedFriProof.prove(dev([v for c in codes for v in c]), m, Transcript())
+    assert got.batch_commitment == want.batch_commitment
+    assert got.commitments == want.commitments
+    assert got.last_elem == want.last_elem and got.last_random == want.last_random
+    assert bytes(got._q) == _flat_batched_queries(want)
+    assert got.verify()
+
+
+@pytest.mark.parametrize("m,log_code", [(2, 2), (2, 6)])
+def test_batched_fri_prover_steps_not_rs_code(m, log_code):
+    """The same non-codewords through the step API (host transcript):
+    batched_fold_step, then the inner fold_steps.  The step at which the oracle
+    hits its "not an RS code" assertion -- the batched step at log_code 2, the
+    last inner step at log_code 6 -- returns MLH_ERR_NOT_RS_CODE and absorbs
+    nothing; every earlier step matches the oracle's roots and transcript."""
+    from multilinear_amd.batched import BatchedFriProverData
+    from oracle import batched as OB
+
+    L, n = log_code, 1 << log_code
+    gp = F.pow_2_generator_powers(L)
+    vals = rand_vals(m * n, 80 + L)
+    otr, tr = OT.Transcript(), Transcript()
+    opd = OB.BatchedFriProverData.init([vals[j * n:(j + 1) * n] for j in range(m)], otr)
+    bp = BatchedFriProverData.init(dev(vals), m, tr)
+    assert bp.batch_root == opd.batch_layer.root() and bp.fingerprint_r == opd.fingerprint_r
+    fd = bp.fri_data
+    failed_at = None
+    for k in range(L - 1):
+        r = tr.next_challenge()
+        assert r == otr.next_challenge()
+        if k == 0:
+            ostep = lambda: opd.batched_fold_step(gp, r, otr)  # noqa: E731
+            step = lambda: bp.batched_fold_step((gp[1], L), r, tr)  # noqa: E731
+        else:
+            ostep = lambda: opd.fri_data.fold_step(gp, k, r, otr)  # noqa: E731
+            step = lambda: fd.fold_step(k, r, tr, gen_pows=(gp[1], L))  # noqa: E731
+        try:
+            ostep()
+        except AssertionError as a:
+            assert "not an RS code" in str(a)
+            with pytest.raises(_lib.MlhError) as e:
+                step()
+            assert e.value.status == _lib.MLH_ERR_NOT_RS_CODE
+            assert tr.random() == otr.random()
+            failed_at = k
+            break
+        step()
+        assert fd.fold_roots() == opd.fri_data.fold_roots(), k
+        assert tr.random() == otr.random(), k
+    assert failed_at == L - 2
+
+
 def test_fri_fold_step_huge_k_rejected():
     """k large enough that (n/2 - 1) 2^k wraps 64 bits is still rejected
     (MLH_ERR_INVALID, the reference's usize index underflow), not folded."""
