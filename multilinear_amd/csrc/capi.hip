@@ -2,12 +2,10 @@
 // host orchestration only, no kernel lives here.
 //
 // Here: the context, the pool and the twiddle-table cache, the NTT /
-// Reed-Solomon / Merkle / field entries, and the provers above FRI --
-//   SumcheckTables::compute_sumcheck_polynomial(s)   sumcheck.rs:77-202
-//   PCSProof::prove                                  multilinear_pcs.rs:90-136
-//   BatchedPCSProof::prove                           batched_pcs.rs:127-180
-// the trace commitment, the constraint-system sumcheck and the system proofs.
-// The FRI prover is fri_prover.hip; verifiers and host transcript, verify.cpp.
+// Reed-Solomon / Merkle / field entries, the stepwise sumcheck entries, the
+// trace commitment, the constraint-system sumcheck and the system proofs.
+// The FRI prover is fri_prover.hip; the sumcheck, PCS and batched-PCS provers
+// above it, pcs_prover.hip; verifiers and host transcript, verify.cpp.
 // Every large vector is device resident; only roots, round sums (32 B each),
 // the last element and the opened query paths cross PCIe.  The whole-proof
 // entries run the Fiat-Shamir transcript on the device (FriDevLoop): the kernel
@@ -29,7 +27,6 @@
 
 #include "../../include/mlhip.h"
 #include "field.hpp"
-#include "batched.hpp"
 #include "dist.hpp"
 #include "fieldops.hpp"
 #include "host_field.hpp"
@@ -42,6 +39,7 @@
 #include "fused_ntt.hpp"
 #include "merkle.hpp"
 #include "ntt.hpp"
+#include "pcs_prover.hpp"
 #include "sha256.hpp"
 #include "sumcheck.hpp"
 #include "system_head.hpp"
@@ -132,10 +130,6 @@ static mlh_status get_table2d(mlh_ctx* ctx, u128 base, uint64_t rows, uint64_t c
                                   expand));
   *out = d;
   return MLH_OK;
-}
-
-static CoopCtl coop_ctl(mlh_ctx* ctx) {
-  return CoopCtl{const_cast<uint32_t*>(ctx->dev_status), ctx->coop_spin};
 }
 
 static uint64_t hi_count(uint32_t log_n) {
@@ -1042,480 +1036,6 @@ mlh_status mlh_sumcheck_fold_and_sums(mlh_ctx* ctx, void* dev_matrix, void* dev_
 
 extern "C" {
 
-mlh_status mlh_sumcheck_prove(mlh_ctx* ctx, void* dev_matrix, void* dev_delta, uint32_t log_height,
-                              const uint8_t sum[16], mlh_transcript* tr, uint8_t* polys_out,
-                              uint8_t* rs_out) {
-  if (!ctx || !dev_matrix || !dev_delta || !sum || !tr || log_height < 1 || log_height > 40)
-    return fail(ctx, MLH_ERR_INVALID, "bad argument");
-  // transcript on the device (one sync): [DevSha | prev | polys 32 x L | rs 16 x L]
-  const uint32_t L = log_height;
-  PoolBuf sc(ctx);
-  MLH_TRY(sc.alloc(128 + 16 + 48ull * L));
-  uint8_t* sb = sc.as<uint8_t>();
-  DevSha* dt = reinterpret_cast<DevSha*>(sb);
-  fe* prev = reinterpret_cast<fe*>(sb + 128);
-  fe* polys = reinterpret_cast<fe*>(sb + 144);
-  fe* rs = reinterpret_cast<fe*>(sb + 144 + 32ull * L);
-  memcpy(ctx->pinned, &tr->sha, sizeof(DevSha));
-  memcpy(ctx->pinned + 128, sum, 16);
-  HIP_TRY(ctx, hipMemcpyAsync(sb, ctx->pinned, 144, hipMemcpyHostToDevice, ctx->stream));
-  fe* m = reinterpret_cast<fe*>(dev_matrix);
-  fe* d = reinterpret_cast<fe*>(dev_delta);
-  // rounds on tables > 2^tail entries: partial-sum kernels over HBM + the
-  // one-lane round kernel; the last `tail` rounds in one LDS-resident launch
-  const uint32_t tail = sumcheck_tail_rounds(L);
-  uint32_t np = 0;
-  if (L > tail)
-    HIP_TRY(ctx, launch_sums(m, d, 1ull << (L - 1), ctx->partials, ctx->small, ctx->stream, &np));
-  for (uint32_t k = 0; k + tail < L; ++k) {
-    HIP_TRY(ctx, launch_sumcheck_round(ctx->partials, np, prev, dt, polys + 2 * k, rs + k,
-                                       ctx->stream));
-    const uint64_t S = 1ull << (L - k);
-    if (k + 1 + tail < L)  // the next round is not a tail round: fold + its sums
-      HIP_TRY(ctx, launch_fold_sums(m, d, S, fe{}, ctx->partials, ctx->small, ctx->stream, rs + k,
-                                    &np));
-    else
-      HIP_TRY(ctx, launch_fold(m, d, S, fe{}, ctx->stream, rs + k));
-  }
-  HIP_TRY(ctx, launch_sumcheck_tail(m, d, tail, prev, dt, polys + 2 * (L - tail),
-                                    rs + (L - tail), ctx->stream));
-  std::vector<uint8_t> host(48ull * L);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, polys, 48ull * L, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(host.data(), ctx->pinned, 48ull * L);
-  ReplayCheck rc(ctx, tr);
-  for (uint32_t k = 0; k < L; ++k) {  // host transcript replay (sumcheck.rs:188-199)
-    rc.absorb(host.data() + 32 * k, 16);
-    rc.absorb(host.data() + 32 * k + 16, 16);
-    rc.expect(host.data() + 32ull * L + 16 * k);
-  }
-  MLH_TRY(rc.status());
-  if (polys_out) memcpy(polys_out, host.data(), 32ull * L);
-  if (rs_out) memcpy(rs_out, host.data() + 32ull * L, 16ull * L);
-  return MLH_OK;
-}
-
-// ---------------------------------------------------------------------------
-// multilinear PCS
-// ---------------------------------------------------------------------------
-// Sumcheck fold (+ the next round's partial sums) of a device-resident round,
-// r read from HBM.  (Running it on a second stream beside the FRI fold_step,
-// which needs the same r, measured no faster: the tree tail it would fill is
-// a handful of waves, and the cross-stream events cost about what it saved.)
-static mlh_status sumcheck_fold_dr(mlh_ctx* ctx, fe* m, fe* d, uint64_t S, const fe* r_dev,
-                                   uint32_t* np, const fe* m_src = nullptr) {
-  if (S >= 4)
-    HIP_TRY(ctx, launch_fold_sums(m, d, S, fe{}, ctx->partials, ctx->small, ctx->stream, r_dev, np,
-                                  m_src));
-  else
-    HIP_TRY(ctx, launch_fold(m, d, S, fe{}, ctx->stream, r_dev, m_src));
-  return MLH_OK;
-}
-
-// Sumcheck over SumcheckTables::build_tables_for_pcs (sumcheck.rs:128-145:
-// matrix, delta = eq(points)) with delta kept factored while the tables are
-// larger than 2^a entries (sumcheck.hip, "eq-factored rounds"): rounds
-// k < B = L - a stream only the matrix and carry delta as c_k * eq(p_k..);
-// folding round B-1 writes delta_B = c_B * eq(p_B..p_{L-1}) (2^a entries) and
-// the remaining rounds run the two-table kernels on it.  Round polynomials,
-// challenges and the folded matrix equal those of the materialised tables.
-#ifndef MLH_TAIL_XC
-#define MLH_TAIL_XC 1  // 0: the tail launch sums its group-A corners itself
-#endif
-#ifndef MLH_TAIL_RSUF
-#define MLH_TAIL_RSUF 1  // 0: the tail launch computes its suffix products itself
-#endif
-struct EqSumcheck {
-  static constexpr uint32_t kEqLo = 12;  // = sumcheck_tail_rounds' LDS limit
-  mlh_ctx* ctx;
-  const fe* src = nullptr;  // round 0's matrix (read only)
-  fe* m = nullptr;          // the folded matrix (== src: folded in place)
-  uint32_t L = 0, a = 0, B = 0;
-  PoolBuf buf;
-  fe *pts = nullptr, *c = nullptr, *lo = nullptr, *d = nullptr, *H = nullptr;
-  fe* Hs = nullptr;  // eq suffix tables of the last a points (sumcheck_eq_tail_kernel)
-  uint32_t* kw = nullptr;  // padding-block K + W tables per round (init with a transcript)
-  fe* wts = nullptr;       // eq weights of the last finished group's challenges (its fold)
-  uint32_t tail_xc_nb = 0; // head_rounds: the tail's group-A corner sums are in ctx->partials
-  bool tail_tables = false; // Hs filled (init's want_tail)
-  fe* rsuf = nullptr;       // the tail's suffix products (want_tail; eq_setup_kernel)
-  explicit EqSumcheck(mlh_ctx* c_) : ctx(c_), buf(c_) {}
-
-  // matrix: round 0's table; work (2^(L-1) entries, optional) receives the
-  // folded table -- the first fold reads `matrix` and writes `work`, so the
-  // caller's evaluations are never copied (build_tables_for_pcs's clone)
-  // sha / sum / dt_out / prev_out (optional): also place the transcript state
-  // and the claimed sum on the device in the same launch
-  mlh_status init(const fe* matrix, fe* work, uint32_t L_, const uint8_t* host_points,
-                  bool want_tail = false, const void* sha = nullptr, const uint8_t* sum = nullptr,
-                  DevSha* dt_out = nullptr, fe* prev_out = nullptr) {
-    src = matrix;
-    m = work ? work : const_cast<fe*>(matrix);
-    L = L_;
-    tail_tables = want_tail;
-    a = L < kEqLo ? L : kEqLo;
-    B = L - a;
-    // c | lo[2^a] | d[2^a] | H[2^B - 1] | Hs[2^a - 1] | pts[L] | kw[64 L words] | wts[64] |
-    // rsuf[2 kEqTailRsuf] (tail, head)
-    MLH_TRY(buf.alloc(16 * (1 + 3 * (1ull << a) + (1ull << B) + L + 16ull * L + 64 + 2 * kEqTailRsuf)));
-    c = buf.as<fe>();
-    lo = c + 1;
-    d = B ? lo + (1ull << a) : lo;  // B == 0: delta is the whole eq table
-    H = lo + 2 * (1ull << a);
-    Hs = H + (1ull << B);
-    pts = Hs + (1ull << a);
-    kw = sha ? reinterpret_cast<uint32_t*>(pts + L) : nullptr;
-    wts = pts + L + 16ull * L;
-    rsuf = MLH_TAIL_RSUF && want_tail ? wts + 64 : nullptr;
-    EqSetupArgs args{};
-    if (L) memcpy(args.pts, host_points, 16ull * L);
-    if (sha) memcpy(&args.sha, sha, sizeof(DevSha));
-    if (sum) memcpy(&args.sum, sum, 16);
-    args.L = L;
-    args.B = B;
-    HIP_TRY(ctx, launch_eq_setup(args, pts, c, lo, H, want_tail ? Hs : nullptr, dt_out, prev_out,
-                                 ctx->stream, kw, rsuf));
-    return MLH_OK;
-  }
-  const fe* Hk(uint32_t k) const { return H + ((1ull << B) - (1ull << (B - k))); }
-
-  // Head rounds k < B go in groups of up to kGroup (sumcheck.hip, "grouped
-  // eq-factored rounds"): one HBM pass yields the corner sums of a whole
-  // group, the group's rounds run from them, and one pass folds the group's
-  // variables and yields the next group's corner sums.  gk / gJ / gnb: the
-  // current group's first round, size and partial block count.
-  static constexpr uint32_t kGroup = 3;
-  uint32_t gk = 0, gJ = 0, gnb = 0;
-  uint32_t group_len(uint32_t k) const { return B - k < kGroup ? B - k : kGroup; }
-
-  // round 0's sums (B > 0: the first group's corner sums) into ctx->partials
-  mlh_status first_sums(uint32_t* np) {
-    if (B) {
-      gk = 0;
-      gJ = group_len(0);
-      HIP_TRY(ctx, launch_group_sums_eq(src, 1ull << L, gJ, Hk(gJ - 1), lo, a, ctx->partials,
-                                        ctx->stream, &gnb));
-      *np = gnb;
-    } else {
-      HIP_TRY(ctx, launch_sums(src, d, 1ull << (L - 1), ctx->partials, ctx->small, ctx->stream, np));
-    }
-    return MLH_OK;
-  }
-  // round k (r: its challenge slot; the slots of one group are contiguous)
-  mlh_status round(uint32_t k, uint32_t np, fe* prev, DevSha* dt, fe* poly, fe* r) {
-    if (k < B) {
-      const uint32_t t = k - gk;
-      HIP_TRY(ctx, launch_sumcheck_group(ctx->partials, gnb, gJ, 0, t, t + 1, prev, dt, poly, r - t,
-                                         pts + gk, c, ctx->stream, coop_ctl(ctx), nullptr, wts));
-    } else {
-      HIP_TRY(ctx, launch_sumcheck_round(ctx->partials, np, prev, dt, poly, r, ctx->stream));
-    }
-    return MLH_OK;
-  }
-  // The head of a prove with no work between rounds (mlh_sumcheck_prove_eq):
-  // passes of up to 6 rounds (two chained groups of <= 3 from one set of
-  // corner sums), each folded in one HBM pass that also sums the next; the
-  // last pass's fold leaves T_B (2^a entries) in m for the tail.
-  mlh_status head_rounds(fe* prev, DevSha* dt, fe* polys, fe* rs) {
-    if (!B) return MLH_OK;
-    if (B <= kEqLo && a == kEqLo && B >= 2) {
-      // B <= 12: one pass for the B-variable corner sums Y, all B rounds in one
-      // launch on Y (two corner groups), then the B-variable fold of the table
-      // as two eq-weighted passes (sumcheck.hip "grouped eq-factored rounds")
-      PoolBuf yb(ctx);
-      MLH_TRY(yb.alloc(16 * ((1ull << B) + 128)));
-      fe* Y = yb.as<fe>();
-      fe* wf = Y + (1ull << B);
-      const uint32_t JA = B < 6 ? B : 6, JB = B - JA;
-      HIP_TRY(ctx, launch_corner_sums_lo(src, B, a, lo, Y, ctx->stream));
-      HIP_TRY(ctx, launch_sumcheck_eq_head(Y, B, Hk(JA - 1), pts, c, prev, dt, polys, rs, wf,
-                                           ctx->stream, coop_ctl(ctx), kw,
-                                           rsuf ? rsuf + kEqTailRsuf : nullptr));
-      // the last fold also sums the tail's group-A corners (JN = 6 over its
-      // 2^12 outputs, e = Hs_5, H = H_{B-1} = [1]): the tail launch then skips
-      // that phase of its prologue (tail_xc_nb partials per corner in
-      // ctx->partials; tail launch 59.3 -> 56.5 us, the fold +1 us)
-      const bool xc = MLH_TAIL_XC && tail_tables;
-      const fe* e5 = Hs + ((1ull << a) - (1ull << (a - 5)));
-      uint32_t nb = 0;
-      HIP_TRY(ctx, launch_fold_group_eq(src, 1ull << L, JA, xc && !JB ? 6 : 0, rs, wf, m,
-                                        xc && !JB ? Hk(B - 1) : nullptr, xc && !JB ? e5 : lo,
-                                        xc && !JB ? 6 : a, ctx->partials, ctx->stream, &nb));
-      if (JB)
-        HIP_TRY(ctx, launch_fold_group_eq(m, 1ull << (L - JA), JB, xc ? 6 : 0, rs + JA, wf + 64, m,
-                                          xc ? Hk(B - 1) : nullptr, xc ? e5 : lo, xc ? 6 : a, ctx->partials,
-                                          ctx->stream, &nb));
-      tail_xc_nb = xc ? nb : 0;
-      return MLH_OK;
-    }
-    uint32_t nb = 0, k = 0, JT = B < kMaxGroup ? B : kMaxGroup;
-    HIP_TRY(ctx, launch_group_sums_eq(src, 1ull << L, JT, Hk(JT - 1), lo, a, ctx->partials,
-                                      ctx->stream, &nb));
-    for (;;) {
-      const uint32_t J1 = JT < 3 ? JT : 3;
-      HIP_TRY(ctx, launch_sumcheck_group(ctx->partials, nb, J1, JT - J1, 0, J1, prev, dt,
-                                         polys + 2 * k, rs + k, pts + k, c, ctx->stream,
-                                         coop_ctl(ctx), kw ? kw + 64 * k : nullptr, wts));
-      const fe* in = k == 0 ? src : m;
-      const uint64_t S = 1ull << (L - k);
-      k += JT;
-      const uint32_t JN = B - k < kMaxGroup ? B - k : kMaxGroup;
-      HIP_TRY(ctx, launch_fold_group_eq(in, S, JT, JN, rs + k - JT, wts, m,
-                                        JN ? Hk(k + JN - 1) : nullptr, lo, a, ctx->partials,
-                                        ctx->stream, &nb));
-      if (!JN) return MLH_OK;
-      JT = JN;
-    }
-  }
-  // after round k's challenge (r_dev): fold what is due (HBM); want_sums: also
-  // round k+1's sums.  A head group folds once, after its last round.
-  mlh_status fold(uint32_t k, const fe* r_dev, uint32_t* np, bool want_sums = true) {
-    const uint64_t S = 1ull << (L - k);
-    if (k < B) {
-      if (k + 1 < gk + gJ) return MLH_OK;  // mid-group: nothing to fold yet
-      const fe* in = gk == 0 ? src : m;
-      const uint32_t JN = group_len(k + 1);
-      HIP_TRY(ctx, launch_fold_group_eq(in, 1ull << (L - gk), gJ, JN, r_dev - (gJ - 1), wts, m,
-                                        JN ? Hk(k + JN) : nullptr, lo, a, ctx->partials,
-                                        ctx->stream, &gnb));
-      if (JN) {
-        gk = k + 1;
-        gJ = JN;
-        *np = gnb;
-        return MLH_OK;
-      }
-      HIP_TRY(ctx, launch_scale_dev(lo, c, 1ull << a, d, ctx->stream));
-      if (want_sums)
-        HIP_TRY(ctx, launch_sums(m, d, 1ull << (a - 1), ctx->partials, ctx->small, ctx->stream, np));
-    } else {
-      MLH_TRY(sumcheck_fold_dr(ctx, m, d, S, r_dev, np, k == 0 ? src : m));
-    }
-    return MLH_OK;
-  }
-};
-
-mlh_status mlh_sumcheck_prove_eq(mlh_ctx* ctx, const void* dev_evals, void* dev_work,
-                                 uint32_t log_height, const uint8_t* host_points,
-                                 const uint8_t sum[16], mlh_transcript* tr, uint8_t* polys_out,
-                                 uint8_t* rs_out, uint8_t* delta_out) {
-  if (!ctx || !dev_evals || !host_points || !sum || !tr || log_height < 1 || log_height > 40)
-    return fail(ctx, MLH_ERR_INVALID, "bad argument");
-  const uint32_t L = log_height;
-  PoolBuf sc(ctx);
-  MLH_TRY(sc.alloc(128 + 16 + 48ull * L + 16));
-  uint8_t* sb = sc.as<uint8_t>();
-  DevSha* dt = reinterpret_cast<DevSha*>(sb);
-  fe* prev = reinterpret_cast<fe*>(sb + 128);
-  fe* polys = reinterpret_cast<fe*>(sb + 144);
-  fe* rs = reinterpret_cast<fe*>(sb + 144 + 32ull * L);
-  fe* dfin = reinterpret_cast<fe*>(sb + 144 + 48ull * L);  // the final delta
-  EqSumcheck es(ctx);  // its setup launch also places the transcript state and the claim
-  device_arm(ctx);
-  MLH_TRY(es.init(reinterpret_cast<const fe*>(dev_evals), reinterpret_cast<fe*>(dev_work), L,
-                  host_points, true, &tr->sha, sum, dt, prev));
-  // head rounds stream only the matrix (passes of up to 6 rounds); the last a
-  // rounds run in the LDS-resident eq tail on the 2^a-entry folded table
-  MLH_TRY(es.head_rounds(prev, dt, polys, rs));
-  HIP_TRY(ctx, launch_sumcheck_eq_tail(es.B ? es.m : es.src, 0, nullptr, es.a, es.Hs,
-                                       es.pts + es.B, es.c, prev, dt, polys + 2 * es.B, rs + es.B,
-                                       es.m, dfin, ctx->stream, coop_ctl(ctx),
-                                       es.kw ? es.kw + 64 * es.B : nullptr,
-                                       HostOut{reinterpret_cast<const uint8_t*>(polys), ctx->pinned,
-                                               (uint32_t)(48ull * L + 16)},
-                                       es.tail_xc_nb ? ctx->partials : nullptr, es.tail_xc_nb,
-                                       es.rsuf));
-  HIP_TRY(ctx, prove_wait(ctx));
-  MLH_TRY(device_check(ctx));
-  std::vector<uint8_t> host(ctx->pinned, ctx->pinned + 48ull * L + 16);
-  ReplayCheck rc(ctx, tr);
-  for (uint32_t k = 0; k < L; ++k) {  // host transcript replay (sumcheck.rs:188-199)
-    rc.absorb(host.data() + 32 * k, 16);
-    rc.absorb(host.data() + 32 * k + 16, 16);
-    rc.expect(host.data() + 32ull * L + 16 * k);
-  }
-  MLH_TRY(rc.status());
-  if (polys_out) memcpy(polys_out, host.data(), 32ull * L);
-  if (rs_out) memcpy(rs_out, host.data() + 32ull * L, 16ull * L);
-  if (delta_out) memcpy(delta_out, host.data() + 48ull * L, 16);
-  return MLH_OK;
-}
-
-// PCSProverData::fold (multilinear_pcs.rs:43-76) for n_vars <= 24, with the
-// sumcheck off the transcript chain (sumcheck.hip "PCS rounds off the
-// transcript kernel"): round k's (c1, c2) come from a one-workgroup job on
-// the eq-factored table once r_{k-1} exists -- an extra workgroup of FRI step
-// k-1's fold launch -- and the launch that writes FRI root k absorbs root k,
-// then (c1, c2)_k, and draws r_k: the transcript order of the reference
-// (root_k | c1_k | c2_k -> r_k), with no sumcheck launch between challenges.
-// Head (the first B = n - 12 variables): the 2^B corner sums of the 2^n table
-// in one pass; after r_{B-1} two fold_group_eq passes fold the table to the
-// 2^12 entries the tail rounds use.  Shared by the PCS and the batched PCS.
-struct PcsRounds {
-  static constexpr uint32_t kMaxVars = 2 * EqSumcheck::kEqLo;
-  mlh_ctx* ctx;
-  FriDevLoop& lp;
-  EqSumcheck es;
-  PoolBuf yb;
-  const fe* evals = nullptr;
-  fe* work = nullptr;
-  fe* Y = nullptr;   // head table: the 2^B corner sums, folded in place
-  fe* wf = nullptr;  // the two fold_group_eq passes' weights
-  PcsRoundState* st = nullptr;
-  uint32_t n = 0, B = 0, a = 0;
-  PcsRounds(mlh_ctx* c, FriDevLoop& l) : ctx(c), lp(l), es(c), yb(c) {}
-
-  // after lp.layout(.., >= 5 extra slots): tables, round state (claim =
-  // claim_host, or claim_dev copied on the device), round 0's polynomial
-  mlh_status init(const fe* evals_, fe* work_, uint32_t n_, const uint8_t* host_inputs,
-                  const uint8_t* claim_host, const fe* claim_dev) {
-    evals = evals_;
-    work = work_;
-    n = n_;
-    MLH_TRY(es.init(evals, work, n, host_inputs, /*want_tail=*/true));
-    B = es.B;
-    a = es.a;
-    if (B) {
-      MLH_TRY(yb.alloc(16 * ((1ull << B) + 128)));
-      Y = yb.as<fe>();
-      wf = Y + (1ull << B);
-    }
-    uint8_t init_state[80] = {};  // (claim, c = 1, e0 = c1 = c2 = 0)
-    if (claim_host) memcpy(init_state, claim_host, 16);
-    init_state[16] = 1;
-    memcpy(ctx->pinned + kPinSlotA, init_state, 80);
-    st = reinterpret_cast<PcsRoundState*>(lp.extra());
-    HIP_TRY(ctx, hipMemcpyAsync(st, ctx->pinned + kPinSlotA, 80, hipMemcpyHostToDevice, ctx->stream));
-    if (claim_dev)
-      HIP_TRY(ctx, hipMemcpyAsync(&st->claim, claim_dev, 16, hipMemcpyDeviceToDevice, ctx->stream));
-    if (B) {
-      HIP_TRY(ctx, launch_corner_sums_lo(evals, B, a, es.lo, Y, ctx->stream));
-      HIP_TRY(ctx, launch_pcs_round(Y, Y, B, false, nullptr, nullptr, es.pts, e_of(0), st, lp.poly(0),
-                                    ctx->stream));
-    } else {
-      HIP_TRY(ctx, launch_pcs_round(evals, work, n, false, nullptr, nullptr, es.pts, e_of(0), st,
-                                    lp.poly(0), ctx->stream));
-    }
-    return MLH_OK;
-  }
-  // e of round k: H_k (head) or Hs_{k-B} (tail); 2^(h-1) entries for a table of 2^h
-  const fe* e_of(uint32_t k) const {
-    return k < B ? es.Hk(k) : es.Hs + ((1ull << a) - (1ull << (a - (k - B))));
-  }
-  // round kn (>= 1) as a job; at kn == B the table fold over the head
-  // variables is enqueued first (it needs r_0..r_{B-1})
-  mlh_status job(uint32_t kn, PcsJob* out) {
-    const uint32_t k = kn - 1;
-    PcsJob j{nullptr, work, 0, 1, lp.r(k), es.pts + k, es.pts + kn, e_of(kn), st, lp.poly(kn)};
-    if (kn < B) {  // head: fold Y with r_k
-      j.src = Y;
-      j.dst = Y;
-      j.log_h = B - kn;
-    } else if (kn == B) {  // fold the table over the B head variables; round B on it
-      const uint32_t JA = B < 6 ? B : 6, JB = B - JA;
-      uint32_t nb = 0;
-      HIP_TRY(ctx, launch_eq_weights(lp.r(0), JA, JB, wf, ctx->stream));
-      HIP_TRY(ctx, launch_fold_group_eq(evals, 1ull << n, JA, 0, lp.r(0), wf, work, nullptr, es.lo, a,
-                                        ctx->partials, ctx->stream, &nb));
-      if (JB)
-        HIP_TRY(ctx, launch_fold_group_eq(work, 1ull << (n - JA), JB, 0, lp.r(JA), wf + 64, work,
-                                          nullptr, es.lo, a, ctx->partials, ctx->stream, &nb));
-      j.src = work;
-      j.log_h = a;
-      j.fold = 0;
-    } else {  // tail: fold with r_k (the first tail fold of B = 0 reads the evaluations)
-      j.src = (B == 0 && kn == 1) ? evals : work;
-      j.log_h = n - kn;
-    }
-    *out = j;
-    return MLH_OK;
-  }
-};
-
-static mlh_status pcs_rounds_fused(mlh_ctx* ctx, FriDevLoop& lp, const fe* evals, fe* work,
-                                   uint32_t n, const uint8_t* host_inputs, const uint8_t output[16],
-                                   const void* code, uint32_t log_domain, mlh_transcript* tr) {
-  MLH_TRY(lp.layout(log_domain, tr, 5));
-  PcsRounds pr(ctx, lp);
-  MLH_TRY(pr.init(evals, work, n, host_inputs, output, nullptr));
-  // FRI init: root 0 | (c1, c2)_0 -> r_0
-  MLH_TRY(lp.init(code, log_domain, true, lp.poly(0)));
-  for (uint32_t k = 0; k < n; ++k) {
-    const uint32_t kn = k + 1;  // the round whose polynomial follows r_k
-    PcsJob job{};
-    if (kn < n) MLH_TRY(pr.job(kn, &job));
-    MLH_TRY(lp.step(k, lp.r(k), kn < n, kn < n ? lp.poly(kn) : nullptr, kn < n ? &job : nullptr));
-  }
-  return MLH_OK;
-}
-
-mlh_status mlh_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t n_vars,
-                         const uint8_t* host_inputs, const uint8_t output[16], mlh_transcript* tr,
-                         mlh_pcs_proof* proof) {
-  if (!ctx || !dev_evals || !output || !tr || !proof || (n_vars && !host_inputs))
-    return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (n_vars < 1 || n_vars > 36) return fail(ctx, MLH_ERR_INVALID, "n_vars out of range");
-  const uint32_t log_domain = n_vars + MLH_LOG_BLOWUP;
-  const uint64_t n = 1ull << n_vars;
-  const u128 gen = h_pow2_generator(log_domain);  // gen_pows[1] (multilinear_pcs.rs:103-104)
-  uint8_t genb[16];
-  h_store(genb, gen);
-  PoolBuf coeffs(ctx), code(ctx), matrix(ctx);
-  MLH_TRY(coeffs.alloc(n * 16));
-  MLH_TRY(code.alloc(2 * n * 16));
-  MLH_TRY(matrix.alloc(n / 2 * 16));  // the folded table (the first fold reads dev_evals)
-  // to_coefficient (:102), bit reverse (:104), reed_solomon (:107); the copy
-  // and the permutation are folded into the Moebius and first NTT passes
-  HIP_TRY(ctx, launch_mobius(coeffs.as<fe>(), n_vars, false, ctx->stream,
-                             reinterpret_cast<const fe*>(dev_evals)));
-  MLH_TRY(mlh_reed_solomon_brev(ctx, coeffs.p, n_vars, genb, code.p));  // bitrev fused
-  // PCSProverData::init (:28-42) + fold loop (:57-75), transcript on the
-  // device: per round the sumcheck round kernel absorbs (c1, c2) and derives
-  // r, which the sumcheck fold and the FRI fold_step read from HBM.
-  mlh_fri_prover fp(ctx, log_domain);
-  FriDevLoop lp(ctx, &fp);
-  device_arm(ctx);
-  if (n_vars <= ctx->pcs_fused_max) {
-    MLH_TRY(pcs_rounds_fused(ctx, lp, reinterpret_cast<const fe*>(dev_evals), matrix.as<fe>(),
-                             n_vars, host_inputs, output, code.p, log_domain, tr));
-  } else {
-    MLH_TRY(lp.layout(log_domain, tr));
-    MLH_TRY(lp.init(code.p, log_domain, false));
-    EqSumcheck es(ctx);  // delta = eq(inputs), factored (build_tables_for_pcs)
-    MLH_TRY(es.init(reinterpret_cast<const fe*>(dev_evals), matrix.as<fe>(), n_vars, host_inputs));
-    memcpy(ctx->pinned + kPinSlotA, output, 16);
-    HIP_TRY(ctx, hipMemcpyAsync(lp.prev(), ctx->pinned + kPinSlotA, 16, hipMemcpyHostToDevice,
-                                ctx->stream));
-    uint32_t np = 0;
-    MLH_TRY(es.first_sums(&np));
-    for (uint32_t k = 0; k < n_vars; ++k) {
-      MLH_TRY(es.round(k, np, lp.prev(), lp.dt(), lp.poly(k), lp.r(k)));
-      MLH_TRY(es.fold(k, lp.r(k), &np));
-      MLH_TRY(lp.step(k, lp.r(k), false));
-    }
-  }
-  MLH_TRY(lp.finish(32ull * n_vars));
-  // host transcript replay: root_0, then per round (c1, c2), root_{k+1} / last
-  const uint8_t* polys = lp.host_polys();
-  if (proof->sumcheck_polys) memcpy(proof->sumcheck_polys, polys, 32ull * n_vars);
-  ReplayCheck rc(ctx, tr);
-  rc.absorb(fp.layers[0].root, 32);
-  for (uint32_t k = 0; k < n_vars; ++k) {
-    rc.absorb(polys + 32 * k, 16);
-    rc.absorb(polys + 32 * k + 16, 16);
-    rc.expect(lp.host_r(k));
-    if (k + 1 < fp.layers.size())
-      rc.absorb(fp.layers[k + 1].root, 32);
-    else
-      rc.absorb(fp.last, 16);
-  }
-  MLH_TRY(rc.status());
-  return fri_queries(ctx, &fp, tr, &proof->fri);
-}
-
-}  // extern "C"
-
-extern "C" {
-
 mlh_status mlh_merkle_open(mlh_ctx* ctx, const void* dev_layers, uint64_t leaves,
                            const uint64_t* host_idx, uint32_t nq, uint8_t* out) {
   if (!ctx || !dev_layers || (nq && (!host_idx || !out)))
@@ -1591,135 +1111,6 @@ mlh_status mlh_bench_ntt(mlh_ctx* ctx, void* dev_buf, uint32_t log_n, uint32_t i
   (void)hipEventDestroy(b);
   *ms_out = ms / iters;
   return MLH_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// batched PCS (batched_pcs.rs; the batched FRI under it: fri_prover.hip)
-// ---------------------------------------------------------------------------
-// The transcript-independent front of BatchedPCSProof::prove
-// (batched_pcs.rs:135-149): per polynomial to_coefficient, bit reverse and
-// reed_solomon at blow-up 2, into dev_codes ([num_polys][2^(n_vars+1)]).
-static mlh_status batched_pcs_codes(mlh_ctx* ctx, const void* dev_evals, uint32_t num_polys,
-                                    uint32_t n_vars, fe* dev_codes) {
-  const uint64_t n = 1ull << n_vars, N = 2 * n;
-  uint8_t genb[16];
-  h_store(genb, h_pow2_generator(n_vars + MLH_LOG_BLOWUP));
-  PoolBuf coeffs(ctx);
-  MLH_TRY(coeffs.alloc(n * 16));
-  const uint8_t* ev = reinterpret_cast<const uint8_t*>(dev_evals);
-  for (uint32_t j = 0; j < num_polys; ++j) {
-    HIP_TRY(ctx, launch_mobius(coeffs.as<fe>(), n_vars, false, ctx->stream,
-                               reinterpret_cast<const fe*>(ev + (uint64_t)j * n * 16)));
-    MLH_TRY(mlh_reed_solomon_brev(ctx, coeffs.p, n_vars, genb,
-                                  reinterpret_cast<uint8_t*>(dev_codes) + (uint64_t)j * N * 16));
-  }
-  return MLH_OK;
-}
-
-// BatchedPCSProof::prove from the point where the codes exist
-// (batched_pcs.rs:150-180): dev_codes as batched_pcs_codes leaves them,
-// dev_evals the MLEs; built_tree (optional) the batch layer's tree over those
-// codes (FriDevLoop::init_batched).
-static mlh_status batched_pcs_open(mlh_ctx* ctx, const fe* dev_codes, const void* dev_evals,
-                                   const uint8_t* built_tree, uint32_t num_polys, uint32_t n_vars,
-                                   const uint8_t* inputs, const uint8_t* outputs,
-                                   mlh_transcript* tr, mlh_batched_pcs_proof* proof) {
-  const uint32_t log_domain = n_vars + MLH_LOG_BLOWUP;
-  const uint64_t n = 1ull << n_vars;
-  PoolBuf matrix(ctx), outs(ctx);
-  MLH_TRY(matrix.alloc(n * 16));
-  MLH_TRY(outs.alloc(16ull * num_polys));
-  // init (batched_pcs.rs:36-78): absorb the claim, batched FRI init.  The
-  // replay check is armed first: any failure from here on restores the
-  // caller's transcript to its state at entry.
-  ReplayCheck rc(ctx, tr);
-  for (uint32_t i = 0; i < n_vars; ++i) rc.absorb(inputs + 16 * i, 16);
-  for (uint32_t j = 0; j < num_polys; ++j) rc.absorb(outputs + 16 * j, 16);
-  mlh_fri_prover fp(ctx, log_domain);
-  FriDevLoop lp(ctx, &fp);
-  device_arm(ctx);
-  const bool fused = n_vars <= ctx->pcs_fused_max;
-  MLH_TRY(lp.init_batched(dev_codes, num_polys, log_domain, tr, false, fused ? 5 : 0, built_tree));
-  // fingerprinted MLE + eq table; previous_sum = fingerprint(fr, outputs)
-  HIP_TRY(ctx, launch_fingerprint(reinterpret_cast<const fe*>(dev_evals), num_polys, n, lp.fr(),
-                                  matrix.as<fe>(), ctx->stream));
-  {
-    std::vector<uint8_t> ob(outputs, outputs + 16ull * num_polys);
-    HIP_TRY(ctx, hipMemcpyAsync(outs.p, ob.data(), ob.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // ob is pageable and goes out of scope
-  }
-  HIP_TRY(ctx, launch_fingerprint_scalar(outs.as<fe>(), num_polys, lp.fr(), lp.prev(), ctx->stream));
-  if (fused) {  // (batched_pcs.rs:80-125) the PCS rounds off the transcript chain (PcsRounds)
-    PcsRounds pr(ctx, lp);
-    fe* mt = matrix.as<fe>();  // the fingerprinted table is ours: its folds run in place
-    MLH_TRY(pr.init(mt, mt, n_vars, inputs, nullptr, lp.prev()));
-    HIP_TRY(ctx, launch_transcript_absorb(lp.dt(), reinterpret_cast<const uint8_t*>(lp.poly(0)), 32,
-                                          lp.r(0), ctx->stream));  // (c1, c2)_0 -> r_0
-    for (uint32_t k = 0; k < n_vars; ++k) {
-      const uint32_t kn = k + 1;
-      PcsJob job{};
-      if (kn < n_vars) MLH_TRY(pr.job(kn, &job));
-      if (k == 0) {  // the batched step: round 1 as its own launch before its tree's root absorb
-        if (kn < n_vars)
-          HIP_TRY(ctx, launch_pcs_round(job.src, job.dst, job.log_h, job.fold != 0, job.r_prev, job.p_prev,
-                                        job.p_k, job.e, job.st, job.poly_out, ctx->stream));
-        MLH_TRY(lp.step_batched(lp.r(0), kn < n_vars, kn < n_vars ? lp.poly(1) : nullptr));
-      } else {
-        MLH_TRY(lp.step(k, lp.r(k), kn < n_vars, kn < n_vars ? lp.poly(kn) : nullptr,
-                        kn < n_vars ? &job : nullptr));
-      }
-    }
-  } else {
-    EqSumcheck es(ctx);  // delta = eq(inputs), factored
-    MLH_TRY(es.init(matrix.as<fe>(), nullptr, n_vars, inputs));
-    uint32_t np = 0;
-    MLH_TRY(es.first_sums(&np));
-    for (uint32_t k = 0; k < n_vars; ++k) {  // fold (batched_pcs.rs:80-125)
-      MLH_TRY(es.round(k, np, lp.prev(), lp.dt(), lp.poly(k), lp.r(k)));
-      MLH_TRY(es.fold(k, lp.r(k), &np));
-      if (k == 0)
-        MLH_TRY(lp.step_batched(lp.r(0), false));
-      else
-        MLH_TRY(lp.step(k, lp.r(k), false));
-    }
-  }
-  MLH_TRY(lp.finish(32ull * n_vars));
-  // host transcript replay
-  const uint8_t* polys = lp.host_polys();
-  if (proof->sumcheck_polys) memcpy(proof->sumcheck_polys, polys, 32ull * n_vars);
-  rc.absorb(lp.host_broot(), 32);
-  rc.expect(lp.host_fr());
-  rc.absorb(lp.host_fr(), 16);
-  for (uint32_t k = 0; k < n_vars; ++k) {
-    rc.absorb(polys + 32 * k, 16);
-    rc.absorb(polys + 32 * k + 16, 16);
-    rc.expect(lp.host_r(k));
-    if (k < fp.layers.size())
-      rc.absorb(fp.layers[k].root, 32);
-    else
-      rc.absorb(fp.last, 16);
-  }
-  MLH_TRY(rc.status());
-  memcpy(proof->fri.batch_commitment, lp.host_broot(), 32);
-  return batched_queries(ctx, lp, tr, &proof->fri);
-}
-
-extern "C" {
-
-mlh_status mlh_batched_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t num_polys,
-                                 uint32_t n_vars, const uint8_t* inputs, const uint8_t* outputs,
-                                 mlh_transcript* tr, mlh_batched_pcs_proof* proof) {
-  if (!ctx || !dev_evals || !inputs || !outputs || !tr || !proof)
-    return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (num_polys == 0) return fail(ctx, MLH_ERR_INVALID, "no polynomials");
-  if (n_vars < 1 || n_vars > 36) return fail(ctx, MLH_ERR_INVALID, "n_vars out of range");
-  PoolBuf codes(ctx);
-  MLH_TRY(codes.alloc(((uint64_t)num_polys << (n_vars + MLH_LOG_BLOWUP)) * 16));
-  MLH_TRY(batched_pcs_codes(ctx, dev_evals, num_polys, n_vars, codes.as<fe>()));
-  return batched_pcs_open(ctx, codes.as<fe>(), dev_evals, nullptr, num_polys, n_vars, inputs,
-                          outputs, tr, proof);
 }
 
 }  // extern "C"
@@ -2140,22 +1531,13 @@ mlh_status mlh_cs_sumcheck_prove_sums(mlh_ctx* ctx, const mlh_cs_program* prog, 
   CsCall cc(ctx);
   MLH_TRY(cc.init(ctx, prog, host_randoms, host_mask));
   const uint32_t D = cc.dev.D;
-  // [DevSha | claim | polys 16 D x L | rs 16 x L | sum columns: 2 x kCsMaxBlocks partials]; one
-  // sync, at the end
-  const uint64_t out_bytes = 16ull * (D + 1) * L;
-  PoolBuf sc(ctx);
-  MLH_TRY(sc.alloc(144 + out_bytes + (smask ? 32ull * kCsMaxBlocks : 0)));
-  uint8_t* sb = sc.as<uint8_t>();
-  DevSha* dt = reinterpret_cast<DevSha*>(sb);
-  fe* prev = reinterpret_cast<fe*>(sb + 128);
-  fe* polys = reinterpret_cast<fe*>(sb + 144);
-  fe* rs = polys + (uint64_t)D * L;
-  fe* lin = smask ? rs + L : nullptr;
+  // the round buffer, behind its challenges the sum columns' 2 x kCsMaxBlocks
+  // partials; one sync, at the end
+  RoundBuf rb(ctx, D, L);
+  MLH_TRY(rb.alloc(smask ? 32ull * kCsMaxBlocks : 0));
+  fe* lin = smask ? rb.extra() : nullptr;
   const fe fbeta = smask ? to_fe(h_load(beta)) : fe{};
-  static_assert(sizeof(DevSha) <= 128, "DevSha slot");
-  memcpy(ctx->pinned, &tr->sha, sizeof(DevSha));
-  memcpy(ctx->pinned + 128, claim, 16);
-  HIP_TRY(ctx, hipMemcpyAsync(sb, ctx->pinned, 144, hipMemcpyHostToDevice, ctx->stream));
+  MLH_TRY(rb.seed(tr, claim));
   fe* m = reinterpret_cast<fe*>(dev_matrix);
   fe* d = reinterpret_cast<fe*>(dev_delta);
   uint32_t nb = 0;
@@ -2168,34 +1550,26 @@ mlh_status mlh_cs_sumcheck_prove_sums(mlh_ctx* ctx, const mlh_cs_program* prog, 
   for (uint32_t k = 0; k < L; ++k) {
     {
       ProfScope ps(ctx, "cs_round");
-      HIP_TRY(ctx, launch_cs_round(ctx->partials, nb, D, cc.vinv, prev, dt, polys + (uint64_t)D * k,
-                                   rs + k, ctx->stream, lin, fbeta));
+      HIP_TRY(ctx, launch_cs_round(ctx->partials, nb, D, cc.vinv, rb.prev(), rb.dt(), rb.poly(k),
+                                   rb.r(k), ctx->stream, lin, fbeta));
       ps.end();
     }
     const uint64_t S = 1ull << (L - k);
     if (S >= 4) {  // fold with r_k + round k+1's sums, one pass
       ProfScope ps(ctx, "cs_fold_sums");
-      HIP_TRY(ctx, launch_cs_fold_sums(cc.dev, cc.threads, m, d, S, fe{}, rs + k, ctx->partials,
+      HIP_TRY(ctx, launch_cs_fold_sums(cc.dev, cc.threads, m, d, S, fe{}, rb.r(k), ctx->partials,
                                        ctx->stream, &nb, smask, lin));
       ps.end();
     } else {
       ProfScope ps(ctx, "cs_fold");
-      HIP_TRY(ctx, launch_cs_fold(width, m, d, S, fe{}, rs + k, ctx->stream));
+      HIP_TRY(ctx, launch_cs_fold(width, m, d, S, fe{}, rb.r(k), ctx->stream));
       ps.end();
     }
   }
   static_assert(16ull * (kCsMaxDegree + 2) * kCsMaxLogHeight <= kPinStage, "prove staging");
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, polys, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<uint8_t> host(ctx->pinned, ctx->pinned + out_bytes);
-  ReplayCheck rc(ctx, tr);
-  for (uint32_t k = 0; k < L; ++k) {  // host transcript replay (sumcheck.rs:194-198)
-    for (uint32_t j = 0; j < D; ++j) rc.absorb(host.data() + 16ull * (k * D + j), 16);
-    rc.expect(host.data() + 16ull * D * L + 16ull * k);
-  }
-  MLH_TRY(rc.status());
-  if (polys_out) memcpy(polys_out, host.data(), 16ull * D * L);
-  if (rs_out) memcpy(rs_out, host.data() + 16ull * D * L, 16ull * L);
+  MLH_TRY(rb.read_back());
+  MLH_TRY(rb.replay(tr));  // (sumcheck.rs:194-198)
+  rb.copy_out(polys_out, rs_out);
   return MLH_OK;
 }
 

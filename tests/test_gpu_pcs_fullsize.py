@@ -1,6 +1,6 @@
 """Production-shape PCS proves against the C oracle, byte for byte.
 
-`mlh_pcs_prove` has three head shapes (capi.hip `PcsRounds`): n <= 12 no head,
+`mlh_pcs_prove` has three head shapes (pcs_prover.hip `PcsRounds`): n <= 12 no head,
 n = 13..18 one `fold_group_eq` pass, n >= 19 two passes; the batched PCS adds
 the fingerprinted batch layer.  These tests run the shapes the bench and the
 reference's own tests use -- n = 19, 20 (multilinear_pcs_bench_test's evals

@@ -1,12 +1,16 @@
 """The PCS provers' rounds off the transcript chain (sumcheck.hip "PCS rounds
-off the transcript kernel"; capi.hip PcsRounds) against the cooperative
+off the transcript kernel"; pcs_prover.hip PcsRounds) against the cooperative
 one-round-per-launch path, which the oracle pins at n <= 17
 (test_gpu_parity.py::test_pcs_prove_matches_oracle, round 3 on): at the
 sizes whose head / tail splits the oracle tests do not reach -- n = 12 (no
 head), 18 (a 6-variable head: one fold pass), 19 and 20 (two fold passes),
 24 (config 4's size, B = 12) -- the two give byte-identical proofs (round
 polynomials, commitments, last element, final transcript output, every query
-record), and the proof verifies.  Reference: multilinear_pcs.rs:43-136,
+record), and the proof verifies.  n = 13, 14 and 16 (B = 1, 2, 4) are the
+cooperative path's short head groups -- a group of one round, of two, and a
+full group of three followed by one -- with the fused side pinned to the
+oracle at those sizes; the batched (2, 13) and (2, 14) put the batched fold
+step in front of such groups.  Reference: multilinear_pcs.rs:43-136,
 batched_pcs.rs:36-180."""
 import ctypes
 import random
@@ -44,7 +48,7 @@ def _proof_bytes(p):
             fp.query_indices, bytes(fp._q))
 
 
-@pytest.mark.parametrize("n", [12, 18, 19, 20, 24])
+@pytest.mark.parametrize("n", [12, 13, 14, 16, 18, 19, 20, 24])
 def test_pcs_fused_equals_cooperative_path(n):
     r = random.Random(900 + n)
     x = D.random_device(1 << n, 900 + n)
@@ -57,7 +61,7 @@ def test_pcs_fused_equals_cooperative_path(n):
     assert got.verify(Transcript())
 
 
-@pytest.mark.parametrize("m,n", [(2, 12), (3, 19)])
+@pytest.mark.parametrize("m,n", [(2, 12), (2, 13), (2, 14), (3, 19)])
 def test_batched_pcs_fused_equals_cooperative_path(m, n):
     from multilinear_amd.batched import BatchedPCSProof
 
