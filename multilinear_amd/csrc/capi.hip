@@ -5,7 +5,8 @@
 // Reed-Solomon / Merkle / field entries, the stepwise sumcheck entries, the
 // trace commitment, the constraint-system sumcheck and the system proofs.
 // The FRI prover is fri_prover.hip; the sumcheck, PCS and batched-PCS provers
-// above it, pcs_prover.hip; verifiers and host transcript, verify.cpp.
+// above it, pcs_prover.hip; the multi-GPU schedules, sharded.hip, and their
+// rank-local steps, shard_steps.hip; verifiers and host transcript, verify.cpp.
 // Every large vector is device resident; only roots, round sums (32 B each),
 // the last element and the opened query paths cross PCIe.  The whole-proof
 // entries run the Fiat-Shamir transcript on the device (FriDevLoop): the kernel
@@ -108,8 +109,8 @@ static mlh_status table_alloc(mlh_ctx* ctx, const TableKey& k, size_t bytes, fe*
 
 // table[t] = base^t * scale, t < count, cached per context.  expand: 4 fe per
 // entry (t * 2^(32k), k < 4) for fe_mul_pre.
-static mlh_status get_table(mlh_ctx* ctx, u128 base, uint64_t count, u128 scale, const fe** out,
-                            bool expand = false) {
+mlh_status mlh::get_table(mlh_ctx* ctx, u128 base, uint64_t count, u128 scale, const fe** out,
+                          bool expand) {
   TableKey k{base, count, scale, expand ? 1 : 0};
   if (table_hit(ctx, k, out)) return MLH_OK;
   fe* d = nullptr;
@@ -132,7 +133,7 @@ static mlh_status get_table2d(mlh_ctx* ctx, u128 base, uint64_t rows, uint64_t c
   return MLH_OK;
 }
 
-static uint64_t hi_count(uint32_t log_n) {
+uint64_t mlh::hi_count(uint32_t log_n) {
   const uint64_t N = 1ull << log_n;
   return N <= 4096 ? 1 : N / 4096;
 }
@@ -215,7 +216,7 @@ mlh_status mlh::fold_tables_g(mlh_ctx* ctx, u128 g, uint32_t log_len, const fe**
   MLH_TRY(get_table(ctx, h_pow(ginv, 4096), hi_count(log_len), 1, thi));
   return MLH_OK;
 }
-static mlh_status fold_tables(mlh_ctx* ctx, uint32_t log_domain, const fe** tlo, const fe** thi) {
+mlh_status mlh::fold_tables(mlh_ctx* ctx, uint32_t log_domain, const fe** tlo, const fe** thi) {
   return fold_tables_g(ctx, h_pow2_generator(log_domain), log_domain, tlo, thi);
 }
 
@@ -785,108 +786,6 @@ mlh_status mlh_fri_fold(mlh_ctx* ctx, const void* dev_layer, uint32_t log_layer,
 }
 
 // ---------------------------------------------------------------------------
-// sharded building blocks (dist.hip; orchestration in tests/dist_spec.py)
-// ---------------------------------------------------------------------------
-mlh_status mlh_shard_ntt_cross(mlh_ctx* ctx, const void* dev_in, void* dev_out, uint32_t log_n,
-                               uint32_t log_p, uint32_t rank, const uint8_t gen[16], int inverse) {
-  if (!ctx || !dev_in || !dev_out || !gen) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (log_p < 1 || log_p > 4 || log_n < 2 * log_p || log_n > 40)
-    return fail(ctx, MLH_ERR_INVALID, "need 1 <= log_p <= 4 and log_n >= 2 log_p");
-  if (rank >> log_p) return fail(ctx, MLH_ERR_INVALID, "rank out of range");
-  if (dev_in == dev_out) return fail(ctx, MLH_ERR_INVALID, "shard_ntt_cross is out of place");
-  const u128 g = h_load(gen);
-  if (!check_generator(g, log_n)) return fail(ctx, MLH_ERR_BAD_GENERATOR, "generator order != n");
-  const uint64_t P = 1ull << log_p, S = 1ull << (log_n - 2 * log_p);
-  const u128 w = inverse ? h_inv(g) : g;
-  const fe *tlo, *thi, *wp;
-  MLH_TRY(get_table(ctx, w, 4096, 1, &tlo));
-  MLH_TRY(get_table(ctx, h_pow(w, 4096), hi_count(log_n - log_p), 1, &thi));
-  MLH_TRY(get_table(ctx, h_pow(w, 1ull << (log_n - log_p)), P / 2, 1, &wp));
-  const u128 scale = inverse ? h_inv((u128)P) : (u128)1;
-  static const char* labs[2][5] = {{"", "shard_dft<1,0>", "shard_dft<2,0>", "shard_dft<3,0>", "shard_dft<4,0>"},
-                                   {"", "shard_dft<1,1>", "shard_dft<2,1>", "shard_dft<3,1>", "shard_dft<4,1>"}};
-  ProfScope ps(ctx, labs[inverse ? 1 : 0][log_p]);
-  HIP_TRY(ctx, launch_shard_dft(reinterpret_cast<const fe*>(dev_in), reinterpret_cast<fe*>(dev_out),
-                                S, (uint64_t)rank * S, log_p, inverse != 0, tlo, thi, wp,
-                                to_fe(scale), ctx->stream));
-  ps.end();
-  return MLH_OK;
-}
-
-static mlh_status shard_fold_args(mlh_ctx* ctx, const void* a, const void* b, const uint8_t* r,
-                                  uint32_t log_local, uint32_t k, uint32_t log_domain,
-                                  uint32_t log_s, uint32_t log_p, uint32_t rank, ShardMap* m) {
-  if (!ctx || !a || !b || !r) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (log_domain > 40 || log_p > 4 || (rank >> log_p) || log_local < 1 ||
-      log_local + log_p + k != log_domain)
-    return fail(ctx, MLH_ERR_INVALID, "local layer must be 2^(log_domain - k - log_p)");
-  if (log_s + 1 > log_local && log_p > 0)
-    return fail(ctx, MLH_ERR_INVALID, "pairs not local: layer spans < 2 blocks per rank");
-  m->log_s = log_p ? log_s : 40;
-  m->log_p = log_p;
-  m->rank = rank;
-  return MLH_OK;
-}
-
-mlh_status mlh_shard_fri_fold(mlh_ctx* ctx, const void* dev_layer, uint32_t log_local, uint32_t k,
-                              uint32_t log_domain, const uint8_t r[16], void* dev_next,
-                              uint32_t log_s, uint32_t log_p, uint32_t rank) {
-  ShardMap m;
-  MLH_TRY(shard_fold_args(ctx, dev_layer, dev_next, r, log_local, k, log_domain, log_s, log_p,
-                          rank, &m));
-  const fe *tlo, *thi;
-  MLH_TRY(fold_tables(ctx, log_domain, &tlo, &thi));
-  HIP_TRY(ctx, launch_fri_fold(reinterpret_cast<const fe*>(dev_layer), 1ull << log_local,
-                               reinterpret_cast<fe*>(dev_next), to_fe(h_load(r)), tlo, thi, k,
-                               1ull << log_domain, ctx->stream, m));
-  return MLH_OK;
-}
-
-mlh_status mlh_shard_fri_fold_commit(mlh_ctx* ctx, const void* dev_layer, uint32_t log_local,
-                                     uint32_t k, uint32_t log_domain, const uint8_t r[16],
-                                     void* dev_next, void* dev_tree, uint32_t log_s,
-                                     uint32_t log_p, uint32_t rank) {
-  ShardMap m;
-  MLH_TRY(shard_fold_args(ctx, dev_layer, dev_next, r, log_local, k, log_domain, log_s, log_p,
-                          rank, &m));
-  if (!dev_tree) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (log_local < 2 || (log_p && log_s + 2 > log_local))
-    return fail(ctx, MLH_ERR_INVALID, "folded layer's pairs are not local");
-  const fe *tlo, *thi;
-  MLH_TRY(fold_tables(ctx, log_domain, &tlo, &thi));
-  uint8_t* tree = reinterpret_cast<uint8_t*>(dev_tree);
-  HIP_TRY(ctx, launch_fri_fold_commit(reinterpret_cast<const fe*>(dev_layer), 1ull << log_local,
-                                      reinterpret_cast<fe*>(dev_next), tree, to_fe(h_load(r)),
-                                      tlo, thi, k, 1ull << log_domain, ctx->stream, m));
-  return MLH_OK;
-}
-
-mlh_status mlh_merkle_open_pairs(mlh_ctx* ctx, const void* dev_values, uint32_t log_n,
-                                 const void* dev_tree, uint32_t levels, const uint64_t* idx,
-                                 uint32_t nq, uint8_t* out) {
-  if (!ctx || !dev_values || !dev_tree || (nq && (!idx || !out)))
-    return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (log_n < 1 || log_n > 40 || levels > log_n - 1)
-    return fail(ctx, MLH_ERR_INVALID, "levels must be <= log_n - 1");
-  const uint64_t half = 1ull << (log_n - 1);
-  for (uint32_t q = 0; q < nq; ++q)
-    if (idx[q] >= half) return fail(ctx, MLH_ERR_INVALID, "index out of bounds");
-  if (nq == 0) return MLH_OK;
-  const uint64_t rec = 32ull * (1 + levels);
-  PoolBuf didx(ctx), dout(ctx);
-  MLH_TRY(didx.alloc(nq * sizeof(uint64_t)));
-  MLH_TRY(dout.alloc(nq * rec));
-  HIP_TRY(ctx, hipMemcpyAsync(didx.p, idx, nq * sizeof(uint64_t), hipMemcpyHostToDevice,
-                              ctx->stream));
-  HIP_TRY(ctx, launch_open_pairs(reinterpret_cast<const fe*>(dev_values), half,
-                                 reinterpret_cast<const uint8_t*>(dev_tree), levels,
-                                 didx.as<uint64_t>(), nq, dout.as<uint8_t>(), ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(out, dout.p, nq * rec, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return MLH_OK;
-}
-
-// ---------------------------------------------------------------------------
 // multilinear / sumcheck
 // ---------------------------------------------------------------------------
 mlh_status mlh_mle_to_coefficient(mlh_ctx* ctx, void* dev_evals, uint32_t log_n) {
@@ -1247,158 +1146,6 @@ void mlh_trace_commitment_destroy(mlh_trace_commitment* c) {
     (void)hipStreamSynchronize(c->ctx->stream);
     delete c;
   }
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// device-resident transcript + sharded steps that read the challenge from HBM
-// (tests/dist_spec.py fri_prove: no host round trip inside the fold loop)
-// ---------------------------------------------------------------------------
-extern "C" {
-
-uint64_t mlh_device_transcript_bytes(void) { return 128; }
-
-mlh_status mlh_transcript_to_device(mlh_ctx* ctx, const mlh_transcript* tr, void* dev_state) {
-  if (!ctx || !tr || !dev_state) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  std::vector<uint8_t> b(sizeof(DevSha));
-  memcpy(b.data(), &tr->sha, sizeof(DevSha));
-  HIP_TRY(ctx, hipMemcpyAsync(dev_state, b.data(), sizeof(DevSha), hipMemcpyHostToDevice,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return MLH_OK;
-}
-
-mlh_status mlh_transcript_from_device(mlh_ctx* ctx, const void* dev_state, mlh_transcript* tr) {
-  if (!ctx || !tr || !dev_state) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev_state, sizeof(DevSha), hipMemcpyDeviceToHost,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(&tr->sha, ctx->pinned, sizeof(DevSha));
-  return MLH_OK;
-}
-
-mlh_status mlh_device_transcript_absorb(mlh_ctx* ctx, void* dev_state, const void* dev_src,
-                                        uint32_t n, void* dev_challenge) {
-  if (!ctx || !dev_state || (n && !dev_src)) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  HIP_TRY(ctx, launch_transcript_absorb(reinterpret_cast<DevSha*>(dev_state),
-                                        reinterpret_cast<const uint8_t*>(dev_src), n,
-                                        reinterpret_cast<fe*>(dev_challenge), ctx->stream));
-  return MLH_OK;
-}
-
-mlh_status mlh_device_fri_last(mlh_ctx* ctx, const void* dev_vals2, void* dev_state,
-                               void* dev_flag, void* dev_last) {
-  if (!ctx || !dev_vals2 || !dev_state || !dev_flag || !dev_last)
-    return fail(ctx, MLH_ERR_INVALID, "null argument");
-  HIP_TRY(ctx, launch_fri_last(reinterpret_cast<const fe*>(dev_vals2),
-                               reinterpret_cast<DevSha*>(dev_state),
-                               reinterpret_cast<uint32_t*>(dev_flag),
-                               reinterpret_cast<fe*>(dev_last), ctx->stream));
-  return MLH_OK;
-}
-
-mlh_status mlh_shard_fri_fold_dr(mlh_ctx* ctx, const void* dev_layer, uint32_t log_local,
-                                 uint32_t k, uint32_t log_domain, const void* dev_r,
-                                 void* dev_next, uint32_t log_s, uint32_t log_p, uint32_t rank) {
-  ShardMap m;
-  const uint8_t dummy[16] = {0};
-  MLH_TRY(shard_fold_args(ctx, dev_layer, dev_next, dummy, log_local, k, log_domain, log_s, log_p,
-                          rank, &m));
-  if (!dev_r) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  const fe *tlo, *thi;
-  MLH_TRY(fold_tables(ctx, log_domain, &tlo, &thi));
-  HIP_TRY(ctx, launch_fri_fold(reinterpret_cast<const fe*>(dev_layer), 1ull << log_local,
-                               reinterpret_cast<fe*>(dev_next), fe{}, tlo, thi, k,
-                               1ull << log_domain, ctx->stream, m,
-                               reinterpret_cast<const fe*>(dev_r)));
-  return MLH_OK;
-}
-
-mlh_status mlh_shard_fri_fold_commit_dr(mlh_ctx* ctx, const void* dev_layer, uint32_t log_local,
-                                        uint32_t k, uint32_t log_domain, const void* dev_r,
-                                        void* dev_next, void* dev_tree, uint32_t log_s,
-                                        uint32_t log_p, uint32_t rank) {
-  ShardMap m;
-  const uint8_t dummy[16] = {0};
-  MLH_TRY(shard_fold_args(ctx, dev_layer, dev_next, dummy, log_local, k, log_domain, log_s, log_p,
-                          rank, &m));
-  if (!dev_tree || !dev_r) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (log_local < 2 || (log_p && log_s + 2 > log_local))
-    return fail(ctx, MLH_ERR_INVALID, "folded layer's pairs are not local");
-  const fe *tlo, *thi;
-  MLH_TRY(fold_tables(ctx, log_domain, &tlo, &thi));
-  uint8_t* tree = reinterpret_cast<uint8_t*>(dev_tree);
-  HIP_TRY(ctx, launch_fri_fold_commit(reinterpret_cast<const fe*>(dev_layer), 1ull << log_local,
-                                      reinterpret_cast<fe*>(dev_next), tree, fe{}, tlo, thi, k,
-                                      1ull << log_domain, ctx->stream, m,
-                                      reinterpret_cast<const fe*>(dev_r)));
-  return MLH_OK;
-}
-
-mlh_status mlh_merkle_top(mlh_ctx* ctx, const void* dev_gathered, uint32_t P, uint64_t per_rank,
-                          void* dev_levels) {
-  if (!ctx || !dev_gathered || !dev_levels) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  const uint64_t n = (uint64_t)P * per_rank;
-  if (!is_pow2(n)) return fail(ctx, MLH_ERR_NOT_POW2, "top tree size must be a power of two");
-  uint8_t* lv = reinterpret_cast<uint8_t*>(dev_levels);
-  HIP_TRY(ctx, launch_top_reorder(reinterpret_cast<const uint8_t*>(dev_gathered), P, per_rank, lv,
-                                  ctx->stream));
-  HIP_TRY(ctx, launch_merkle_levels(lv, n, ctx->stream));
-  return MLH_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// device-resident sumcheck steps (sharded sumcheck in tests/dist_spec.py)
-// ---------------------------------------------------------------------------
-extern "C" {
-
-mlh_status mlh_sumcheck_sums_dev(mlh_ctx* ctx, const void* dev_matrix, const void* dev_delta,
-                                 uint32_t log_height, void* dev_sums) {
-  if (!ctx || !dev_matrix || !dev_delta || !dev_sums || log_height < 1 || log_height > 40)
-    return fail(ctx, MLH_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, launch_sums(reinterpret_cast<const fe*>(dev_matrix),
-                           reinterpret_cast<const fe*>(dev_delta), 1ull << (log_height - 1),
-                           ctx->partials, reinterpret_cast<fe*>(dev_sums), ctx->stream));
-  return MLH_OK;
-}
-
-mlh_status mlh_sumcheck_fold_sums_dr(mlh_ctx* ctx, void* dev_matrix, void* dev_delta,
-                                     uint32_t log_height, const void* dev_r, void* dev_sums) {
-  if (!ctx || !dev_matrix || !dev_delta || !dev_r || !dev_sums || log_height < 2 ||
-      log_height > 40)
-    return fail(ctx, MLH_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, launch_fold_sums(reinterpret_cast<fe*>(dev_matrix), reinterpret_cast<fe*>(dev_delta),
-                                1ull << log_height, fe{}, ctx->partials,
-                                reinterpret_cast<fe*>(dev_sums), ctx->stream,
-                                reinterpret_cast<const fe*>(dev_r)));
-  return MLH_OK;
-}
-
-mlh_status mlh_sumcheck_fold_dr(mlh_ctx* ctx, void* dev_matrix, void* dev_delta,
-                                uint32_t log_height, const void* dev_r) {
-  if (!ctx || !dev_matrix || !dev_delta || !dev_r || log_height < 1 || log_height > 40)
-    return fail(ctx, MLH_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, launch_fold(reinterpret_cast<fe*>(dev_matrix), reinterpret_cast<fe*>(dev_delta),
-                           1ull << log_height, fe{}, ctx->stream,
-                           reinterpret_cast<const fe*>(dev_r)));
-  return MLH_OK;
-}
-
-mlh_status mlh_device_sumcheck_round(mlh_ctx* ctx, const void* dev_sum_pairs, uint32_t npairs,
-                                     void* dev_prev, void* dev_state, void* dev_poly_out,
-                                     void* dev_r_out) {
-  if (!ctx || !dev_sum_pairs || !dev_prev || !dev_state || !dev_poly_out || !dev_r_out ||
-      npairs == 0)
-    return fail(ctx, MLH_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, launch_sumcheck_round(reinterpret_cast<const fe*>(dev_sum_pairs), npairs,
-                                     reinterpret_cast<fe*>(dev_prev),
-                                     reinterpret_cast<DevSha*>(dev_state),
-                                     reinterpret_cast<fe*>(dev_poly_out),
-                                     reinterpret_cast<fe*>(dev_r_out), ctx->stream));
-  return MLH_OK;
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // Internal state of an mlh_ctx and the helpers every host-side translation
-// unit of libmlhip shares (capi.hip: the single-GPU C ABI; sharded.hip: the
-// multi-GPU orchestration): the device memory pool, the table cache record,
-// error reporting.  Not part of the public C ABI.
+// unit of libmlhip shares (capi.hip: the single-GPU C ABI; fri_prover.hip and
+// pcs_prover.hip: the provers above it; sharded.hip: the multi-GPU
+// orchestration; shard_steps.hip: its rank-local steps): the device memory
+// pool, the table cache record, error reporting.  Not part of the public C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -5,8 +5,9 @@
 // src/fri/mod.rs:19-145 and :261-285, sumcheck.rs:77-247); SURVEY.md 8(e)
 // prescribes the sharding, DESIGN.md §6 describes the layouts.  This is the
 // one product implementation of the schedules (a Rust caller binds it
-// directly); tests/dist_spec.py restates them in Python as the executable spec
-// the CPU gloo tests run with oracle rank-local steps.
+// directly); the steps a rank runs between two collectives are the entries of
+// shard_steps.hip; tests/dist_spec.py restates the schedules in Python as the
+// executable spec the CPU gloo tests run with oracle rank-local steps.
 //
 // Layout: a sharded vector of 2^log_n elements over P = 2^log_p ranks is
 // block-cyclic with block S = 2^log_s: local l of rank r is global
@@ -30,6 +31,8 @@
 #include "fused_ntt.hpp"
 #include "host_sha256.hpp"
 #include "host_transcript.hpp"
+#include "pcs_prover.hpp"
+#include "tables.hpp"
 
 using namespace mlh;
 
@@ -127,7 +130,6 @@ struct Bufs {
 
 void store_fe(uint8_t out[16], u128 v) { h_store(out, v); }
 
-// gen has order exactly 2^log_n (the cross-shard DFT needs a DFT generator)
 // The side streams of the pipelined sharded calls (lazy).  (Giving the
 // exchange stream the device's highest priority measured no change in
 // tools/shard_step_emul.py: 0.766-0.769 vs 0.763 ms a step; not kept.)
@@ -137,10 +139,111 @@ mlh_status ensure_side_streams(mlh_ctx* ctx) {
   return MLH_OK;
 }
 
-bool gen_has_order(u128 gen, uint32_t log_n) {
-  if (gen >= kModulus) return false;
-  if (log_n == 0) return gen == 1;
-  return h_pow(gen, (u128)1 << (log_n - 1)) == kModulus - 1;
+// The arguments of the sharded NTT family, checked before any local work or
+// collective: min_log <= log_n <= 40 (2^log_n >= 2 P^2 is min_log = 2 log P +
+// 1; the fused plan has its own lower bound), gen of order exactly 2^log_n
+// (the cross-shard DFT needs a DFT generator).  gp (optional) = gen^P, the
+// generator of the local transforms.
+mlh_status check_ntt_args(Tp& tp, uint32_t log_n, uint32_t min_log, const uint8_t gen[16],
+                          const char* size_msg, const char* order_msg, uint8_t gp[16]) {
+  if (log_n < min_log || log_n > 40) return fail(tp.ctx, MLH_ERR_INVALID, size_msg);
+  if (!check_generator(h_load(gen), log_n)) return fail(tp.ctx, MLH_ERR_BAD_GENERATOR, order_msg);
+  if (gp) store_fe(gp, h_pow(h_load(gen), (u128)tp.P));
+  return MLH_OK;
+}
+
+// The events of one pipelined call; they go back to the context's free list.
+struct Recycle {
+  mlh_ctx* c;
+  hipEvent_t e[9];
+  explicit Recycle(mlh_ctx* ctx) : c(ctx) {
+    for (hipEvent_t& x : e) x = take_event(ctx);
+  }
+  ~Recycle() {
+    for (hipEvent_t x : e) c->ev_free.push_back(x);
+  }
+};
+
+// On every exit of a pipelined call, error paths included, the context stream
+// waits for all the side streams' work: the pooled buffers and the events
+// (both released after this guard) are reused only behind it.
+struct JoinSide {
+  hipStream_t main, s1, s2;
+  hipEvent_t e1, e2;
+  ~JoinSide() {
+    (void)hipEventRecord(e1, s1);
+    (void)hipStreamWaitEvent(main, e1, 0);
+    (void)hipEventRecord(e2, s2);
+    (void)hipStreamWaitEvent(main, e2, 0);
+  }
+};
+
+// `count` transforms of the shape step A -> all-to-all of bytes_per_rank ->
+// step C: A(i, z) writes the P chunks to send into z, C(i, recv) reads the P
+// received chunks.  lab (optional): the exchanges' kernel-timer label.
+//
+// In turn (pipelined = false: a host-side transport, a single transform): one
+// buffer pair, everything on the context stream.
+//
+// Pipelined over three streams: A on the context stream, the exchange on the
+// side stream, C on a third stream.  So A(i+1), the exchange of i and C(i-1)
+// run at once, and a step costs about max(A || C, exchange): the VALU-bound
+// NTT and the HBM-bound cross-shard DFT share the chip better side by side
+// than in turn (0.566 ms against 0.584 ms for the 2^24 NTT + the
+// P = 8 cross step on one MI355X), and C no longer sits behind the exchange
+// on its stream (0.58-0.74 ms a step at P = 8 for the xGMI rates assumed
+// there).  Buffers: z[k] (A's output, sent) and recv[k] (received, C's
+// input), k = i mod 2; A(i+2) reuses z[k] after the exchange of i sent it;
+// the exchange of i+2 fills recv[k] after C(i) has read it.  On return the
+// context stream is ordered after every transform.
+template <class StepA, class StepC>
+mlh_status run_exchanges(Tp& tp, uint32_t count, uint64_t bytes_per_rank, bool pipelined,
+                         const char* lab, StepA&& A, StepC&& C) {
+  mlh_ctx* ctx = tp.ctx;
+  if (!count) return MLH_OK;
+  if (pipelined) MLH_TRY(ensure_side_streams(ctx));
+  Bufs b(ctx);
+  fe *z[2], *recv[2];
+  for (int k = 0; k < (pipelined ? 2 : 1); ++k) {
+    MLH_TRY(b.get(bytes_per_rank * tp.P, &z[k]));
+    MLH_TRY(b.get(bytes_per_rank * tp.P, &recv[k]));
+  }
+  if (!pipelined) {
+    for (uint32_t i = 0; i < count; ++i) {
+      MLH_TRY(A(i, z[0]));
+      MLH_TRY(tp.all_to_all(z[0], recv[0], bytes_per_rank, lab));
+      MLH_TRY(C(i, recv[0]));
+    }
+    return MLH_OK;
+  }
+  Recycle ev(ctx);
+  hipEvent_t *a_done = ev.e, *x_done = ev.e + 2, *c_done = ev.e + 4;
+  hipStream_t main = ctx->stream, side = ctx->side, third = ctx->side2;
+  // the third stream starts after the caller's work (the side stream's first
+  // wait is on a_done, recorded on the context stream)
+  HIP_TRY(ctx, hipEventRecord(ev.e[8], main));
+  HIP_TRY(ctx, hipStreamWaitEvent(third, ev.e[8], 0));
+  JoinSide join{main, side, third, ev.e[6], ev.e[7]};
+  for (uint32_t i = 0; i < count; ++i) {
+    const int k = i & 1;
+    if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(main, x_done[k], 0));  // z[k] was sent
+    MLH_TRY(A(i, z[k]));
+    HIP_TRY(ctx, hipEventRecord(a_done[k], main));
+    HIP_TRY(ctx, hipStreamWaitEvent(side, a_done[k], 0));
+    if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(side, c_done[k], 0));  // C(i - 2) read recv[k]
+    {
+      StreamSwap sw(ctx, side);
+      MLH_TRY(tp.all_to_all(z[k], recv[k], bytes_per_rank, lab));
+    }
+    HIP_TRY(ctx, hipEventRecord(x_done[k], side));
+    HIP_TRY(ctx, hipStreamWaitEvent(third, x_done[k], 0));
+    {
+      StreamSwap sw(ctx, third);
+      MLH_TRY(C(i, recv[k]));
+    }
+    HIP_TRY(ctx, hipEventRecord(c_done[k], third));
+  }
+  return MLH_OK;  // (join: main waits for both side streams)
 }
 
 }  // namespace
@@ -299,55 +402,47 @@ extern "C" mlh_status mlh_comm_preflight(mlh_ctx* ctx, const mlh_transport* tp, 
 }
 
 // ---------------------------------------------------------------------------
-// NTT / INTT / Reed-Solomon (ntt/mod.rs:69-173, fri/mod.rs:19-28)
+// NTT / INTT / Reed-Solomon (ntt/mod.rs:69-173, fri/mod.rs:19-28): argument
+// checks and run_exchanges with the entry point's two steps
 // ---------------------------------------------------------------------------
 // X[j + M t] = sum_g wP^(g t) w^(g j) Z_g[j], Z_g = NTT_M(x[g + P .]) with
 // generator w^P, M = N / P: local NTT, all-to-all of the M/P-element chunks,
-// cross-shard DFT (mlh_shard_ntt_cross).
+// cross-shard DFT (mlh_shard_ntt_cross); the inverse runs them backwards.
+static mlh_status sharded_ntts(Tp& tp, const void* const* in, void* const* out, uint32_t count,
+                               uint32_t log_n, const uint8_t gen[16], int inverse, bool pipelined) {
+  mlh_ctx* ctx = tp.ctx;
+  if (tp.P == 1) {
+    for (uint32_t i = 0; i < count; ++i)
+      MLH_TRY(inverse ? mlh_intt(ctx, in[i], out[i], log_n, gen) : mlh_ntt(ctx, in[i], out[i], log_n, gen));
+    return MLH_OK;
+  }
+  uint8_t gp[16];
+  MLH_TRY(check_ntt_args(tp, log_n, 2 * tp.p + 1, gen, "sharded NTT needs 2^log_n >= 2 P^2",
+                         "generator order != n", gp));
+  const uint32_t log_m = log_n - tp.p;
+  // (the kernel timer has never labelled the exchange of an inverse transform run in turn)
+  const char* lab = pipelined || !inverse ? "ntt_all_to_all" : nullptr;
+  auto cross = [&](const void* src, void* dst) {
+    return mlh_shard_ntt_cross(ctx, src, dst, log_n, tp.p, tp.rank, gen, inverse);
+  };
+  return run_exchanges(
+      tp, count, (16ull << log_m) / tp.P, pipelined, lab,
+      [&](uint32_t i, fe* z) { return inverse ? cross(in[i], z) : mlh_ntt(ctx, in[i], z, log_m, gp); },
+      [&](uint32_t i, fe* recv) {
+        return inverse ? mlh_intt(ctx, recv, out[i], log_m, gp) : cross(recv, out[i]);
+      });
+}
+
 mlh_status mlh_sharded_ntt(mlh_ctx* ctx, const mlh_transport* t, const void* dev_in, void* dev_out,
                            uint32_t log_n, const uint8_t gen[16], int inverse) {
   if (!ctx || !dev_in || !dev_out || !gen) return fail(ctx, MLH_ERR_INVALID, "null argument");
   MLH_TRY(check_transport(ctx, t));
   Tp tp(ctx, t);
-  if (tp.P == 1)
-    return inverse ? mlh_intt(ctx, dev_in, dev_out, log_n, gen) : mlh_ntt(ctx, dev_in, dev_out, log_n, gen);
-  if (log_n < 2 * tp.p + 1 || log_n > 40)
-    return fail(ctx, MLH_ERR_INVALID, "sharded NTT needs 2^log_n >= 2 P^2");
-  if (!gen_has_order(h_load(gen), log_n))  // before any local work or collective
-    return fail(ctx, MLH_ERR_BAD_GENERATOR, "generator order != n");
-  const uint64_t M = 1ull << (log_n - tp.p);
-  uint8_t gp[16];
-  store_fe(gp, h_pow(h_load(gen), (u128)tp.P));
-  Bufs b(ctx);
-  fe *z, *recv;
-  MLH_TRY(b.get(M * 16, &z));
-  MLH_TRY(b.get(M * 16, &recv));
-  if (!inverse) {
-    MLH_TRY(mlh_ntt(ctx, dev_in, z, log_n - tp.p, gp));
-    MLH_TRY(tp.all_to_all(z, recv, M / tp.P * 16, "ntt_all_to_all"));
-    MLH_TRY(mlh_shard_ntt_cross(ctx, recv, dev_out, log_n, tp.p, tp.rank, gen, 0));
-  } else {
-    MLH_TRY(mlh_shard_ntt_cross(ctx, dev_in, z, log_n, tp.p, tp.rank, gen, 1));
-    MLH_TRY(tp.all_to_all(z, recv, M / tp.P * 16));
-    MLH_TRY(mlh_intt(ctx, recv, dev_out, log_n - tp.p, gp));
-  }
-  return MLH_OK;
+  return sharded_ntts(tp, &dev_in, &dev_out, 1, log_n, gen, inverse, false);
 }
 
-// `count` transforms, pipelined over three streams: the first local step A
-// (forward: the local NTT; inverse: the cross-shard DFT) on the context
-// stream, the exchange on the side stream, the second local step C
-// (forward: the cross-shard DFT; inverse: the local INTT) on a third stream.
-// So A(i+1), the exchange of i and C(i-1) run at once, and a step costs about
-// max(A || C, exchange): the VALU-bound NTT and the HBM-bound cross-shard DFT
-// share the chip better side by side than in turn (0.566 ms
-// against 0.584 ms for the 2^24 NTT + the P = 8 cross step on one MI355X), and
-// C no longer sits behind the exchange on its stream (0.58-0.74 ms a step at
-// P = 8 for the xGMI rates assumed there).  Buffers: z[k] (A's output, sent)
-// and recv[k] (received, C's input), k = i mod 2; A(i+2) reuses z[k] after
-// the exchange of i sent it; the exchange of i+2 fills recv[k] after C(i) has
-// read it.  On return the context stream is ordered after every transform.
-// With a host-side transport the transforms run one after another.
+// `count` transforms, pipelined over three streams (run_exchanges); with a
+// host-side transport they run one after another.
 mlh_status mlh_sharded_ntt_batch(mlh_ctx* ctx, const mlh_transport* t, const void* const* dev_in,
                                  void* const* dev_out, uint32_t count, uint32_t log_n,
                                  const uint8_t gen[16], int inverse) {
@@ -356,81 +451,7 @@ mlh_status mlh_sharded_ntt_batch(mlh_ctx* ctx, const mlh_transport* t, const voi
   for (uint32_t i = 0; i < count; ++i)
     if (!dev_in[i] || !dev_out[i]) return fail(ctx, MLH_ERR_INVALID, "null argument");
   Tp tp(ctx, t);
-  if (tp.P == 1 || t->host_side) {
-    for (uint32_t i = 0; i < count; ++i)
-      MLH_TRY(mlh_sharded_ntt(ctx, t, dev_in[i], dev_out[i], log_n, gen, inverse));
-    return MLH_OK;
-  }
-  if (log_n < 2 * tp.p + 1 || log_n > 40)
-    return fail(ctx, MLH_ERR_INVALID, "sharded NTT needs 2^log_n >= 2 P^2");
-  if (!gen_has_order(h_load(gen), log_n)) return fail(ctx, MLH_ERR_BAD_GENERATOR, "generator order != n");
-  if (!count) return MLH_OK;
-  MLH_TRY(ensure_side_streams(ctx));
-  const uint64_t M = 1ull << (log_n - tp.p);
-  uint8_t gp[16];
-  store_fe(gp, h_pow(h_load(gen), (u128)tp.P));
-  Bufs b(ctx);
-  fe *z[2], *recv[2];
-  for (int k = 0; k < 2; ++k) {
-    MLH_TRY(b.get(M * 16, &z[k]));
-    MLH_TRY(b.get(M * 16, &recv[k]));
-  }
-  hipEvent_t a_done[2], x_done[2], c_done[2];
-  for (int k = 0; k < 2; ++k) {
-    a_done[k] = take_event(ctx);
-    x_done[k] = take_event(ctx);
-    c_done[k] = take_event(ctx);
-  }
-  struct Recycle {  // the events go back to the context's free list
-    mlh_ctx* c;
-    hipEvent_t* e;
-    ~Recycle() {
-      for (int k = 0; k < 9; ++k) c->ev_free.push_back(e[k]);
-    }
-  };
-  hipEvent_t evs[9] = {a_done[0], a_done[1], x_done[0], x_done[1], c_done[0], c_done[1],
-                       take_event(ctx), take_event(ctx), take_event(ctx)};
-  Recycle rec{ctx, evs};
-  hipStream_t main = ctx->stream, side = ctx->side, third = ctx->side2;
-  // the third stream starts after the caller's work (the side stream's first
-  // wait is on a_done, recorded on the context stream)
-  HIP_TRY(ctx, hipEventRecord(evs[8], main));
-  HIP_TRY(ctx, hipStreamWaitEvent(third, evs[8], 0));
-  // On every exit, error paths included, the context stream waits for all the
-  // side streams' work: the pooled buffers (Bufs, released after this guard)
-  // and the events are reused only behind it.
-  struct JoinSide {
-    hipStream_t main, s1, s2;
-    hipEvent_t e1, e2;
-    ~JoinSide() {
-      (void)hipEventRecord(e1, s1);
-      (void)hipStreamWaitEvent(main, e1, 0);
-      (void)hipEventRecord(e2, s2);
-      (void)hipStreamWaitEvent(main, e2, 0);
-    }
-  } join{main, side, third, evs[6], evs[7]};
-  for (uint32_t i = 0; i < count; ++i) {
-    const int k = i & 1;
-    if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(main, x_done[k], 0));  // z[k] was sent
-    if (!inverse) MLH_TRY(mlh_ntt(ctx, dev_in[i], z[k], log_n - tp.p, gp));
-    else MLH_TRY(mlh_shard_ntt_cross(ctx, dev_in[i], z[k], log_n, tp.p, tp.rank, gen, 1));
-    HIP_TRY(ctx, hipEventRecord(a_done[k], main));
-    HIP_TRY(ctx, hipStreamWaitEvent(side, a_done[k], 0));
-    if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(side, c_done[k], 0));  // C(i - 2) read recv[k]
-    {
-      StreamSwap sw(ctx, side);
-      MLH_TRY(tp.all_to_all(z[k], recv[k], M / tp.P * 16, "ntt_all_to_all"));
-    }
-    HIP_TRY(ctx, hipEventRecord(x_done[k], side));
-    HIP_TRY(ctx, hipStreamWaitEvent(third, x_done[k], 0));
-    {
-      StreamSwap sw(ctx, third);
-      if (!inverse) MLH_TRY(mlh_shard_ntt_cross(ctx, recv[k], dev_out[i], log_n, tp.p, tp.rank, gen, 0));
-      else MLH_TRY(mlh_intt(ctx, recv[k], dev_out[i], log_n - tp.p, gp));
-    }
-    HIP_TRY(ctx, hipEventRecord(c_done[k], third));
-  }
-  return MLH_OK;  // (join: main waits for both side streams)
+  return sharded_ntts(tp, dev_in, dev_out, count, log_n, gen, inverse, !t->host_side);
 }
 
 // `count` forward transforms with the rank digit fused into the last pass
@@ -452,75 +473,14 @@ mlh_status mlh_sharded_ntt_fused_batch(mlh_ctx* ctx, const mlh_transport* t, con
     if (!dev_in[i] || !dev_out[i]) return fail(ctx, MLH_ERR_INVALID, "null argument");
   Tp tp(ctx, t);
   if (tp.P < 2 || tp.P > 8) return fail(ctx, MLH_ERR_INVALID, "fused sharded NTT: 2 <= P <= 8");
-  if (log_n > 40) return fail(ctx, MLH_ERR_INVALID, "log_n");
-  if (!gen_has_order(h_load(gen), log_n)) return fail(ctx, MLH_ERR_BAD_GENERATOR, "generator order != n");
+  MLH_TRY(check_ntt_args(tp, log_n, 0, gen, "log_n", "generator order != n", nullptr));
   FusedNtt fz;
   MLH_TRY(fz.prepare(ctx, h_load(gen), log_n, tp.p, tp.rank));
   if (log_s_out) *log_s_out = fz.out_log_s();
-  if (!count) return MLH_OK;
-  const uint64_t M = 1ull << (log_n - tp.p);
-  if (t->host_side) {  // transforms in turn
-    Bufs b(ctx);
-    fe *z, *recv;
-    MLH_TRY(b.get(M * 16, &z));
-    MLH_TRY(b.get(M * 16, &recv));
-    for (uint32_t i = 0; i < count; ++i) {
-      MLH_TRY(fz.run_pre(dev_in[i], z));
-      MLH_TRY(tp.all_to_all(z, recv, M / tp.P * 16, "ntt_all_to_all"));
-      MLH_TRY(fz.run_last(recv, dev_out[i]));
-    }
-    return MLH_OK;
-  }
-  MLH_TRY(ensure_side_streams(ctx));
-  Bufs b(ctx);
-  fe *z[2], *recv[2];
-  for (int k = 0; k < 2; ++k) {
-    MLH_TRY(b.get(M * 16, &z[k]));
-    MLH_TRY(b.get(M * 16, &recv[k]));
-  }
-  hipEvent_t evs[9];
-  for (auto& e : evs) e = take_event(ctx);
-  struct Recycle {
-    mlh_ctx* c;
-    hipEvent_t* e;
-    ~Recycle() {
-      for (int k = 0; k < 9; ++k) c->ev_free.push_back(e[k]);
-    }
-  } rec{ctx, evs};
-  hipEvent_t *a_done = evs, *x_done = evs + 2, *c_done = evs + 4;
-  hipStream_t main = ctx->stream, side = ctx->side, third = ctx->side2;
-  HIP_TRY(ctx, hipEventRecord(evs[8], main));  // the third stream starts after the caller's work
-  HIP_TRY(ctx, hipStreamWaitEvent(third, evs[8], 0));
-  struct JoinSide {  // every exit: the context stream waits for both side streams
-    hipStream_t main, s1, s2;
-    hipEvent_t e1, e2;
-    ~JoinSide() {
-      (void)hipEventRecord(e1, s1);
-      (void)hipStreamWaitEvent(main, e1, 0);
-      (void)hipEventRecord(e2, s2);
-      (void)hipStreamWaitEvent(main, e2, 0);
-    }
-  } join{main, side, third, evs[6], evs[7]};
-  for (uint32_t i = 0; i < count; ++i) {
-    const int k = i & 1;
-    if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(main, x_done[k], 0));  // z[k] was sent
-    MLH_TRY(fz.run_pre(dev_in[i], z[k]));
-    HIP_TRY(ctx, hipEventRecord(a_done[k], main));
-    HIP_TRY(ctx, hipStreamWaitEvent(side, a_done[k], 0));
-    if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(side, c_done[k], 0));  // recv[k] was read
-    {
-      StreamSwap sw(ctx, side);
-      MLH_TRY(tp.all_to_all(z[k], recv[k], M / tp.P * 16, "ntt_all_to_all"));
-    }
-    HIP_TRY(ctx, hipEventRecord(x_done[k], side));
-    HIP_TRY(ctx, hipStreamWaitEvent(third, x_done[k], 0));
-    {
-      StreamSwap sw(ctx, third);
-      MLH_TRY(fz.run_last(recv[k], dev_out[i]));
-    }
-    HIP_TRY(ctx, hipEventRecord(c_done[k], third));
-  }
-  return MLH_OK;
+  return run_exchanges(
+      tp, count, (16ull << (log_n - tp.p)) / tp.P, !t->host_side, "ntt_all_to_all",
+      [&](uint32_t i, fe* z) { return fz.run_pre(dev_in[i], z); },
+      [&](uint32_t i, fe* recv) { return fz.run_last(recv, dev_out[i]); });
 }
 
 mlh_status mlh_sharded_reed_solomon(mlh_ctx* ctx, const mlh_transport* t, const void* dev_coeffs,
@@ -529,21 +489,16 @@ mlh_status mlh_sharded_reed_solomon(mlh_ctx* ctx, const mlh_transport* t, const 
   MLH_TRY(check_transport(ctx, t));
   Tp tp(ctx, t);
   if (tp.P == 1) return mlh_reed_solomon(ctx, dev_coeffs, log_n, gen, dev_code);
-  const uint32_t log_c = log_n + MLH_LOG_BLOWUP;
-  if (log_c < 2 * tp.p + 1 || log_c > 40)
-    return fail(ctx, MLH_ERR_INVALID, "sharded RS needs 2^(log_n+1) >= 2 P^2");
-  if (!gen_has_order(h_load(gen), log_c))
-    return fail(ctx, MLH_ERR_BAD_GENERATOR, "generator order != 2n");
-  const uint64_t M2 = 1ull << (log_c - tp.p);  // local code length
+  const uint32_t log_c = log_n + MLH_LOG_BLOWUP;  // the local code has 2^(log_c - log P) elements
   uint8_t gp[16];
-  store_fe(gp, h_pow(h_load(gen), (u128)tp.P));
-  Bufs b(ctx);
-  fe *z, *recv;
-  MLH_TRY(b.get(M2 * 16, &z));
-  MLH_TRY(b.get(M2 * 16, &recv));
-  MLH_TRY(mlh_reed_solomon(ctx, dev_coeffs, log_n - tp.p, gp, z));
-  MLH_TRY(tp.all_to_all(z, recv, M2 / tp.P * 16));
-  return mlh_shard_ntt_cross(ctx, recv, dev_code, log_c, tp.p, tp.rank, gen, 0);
+  MLH_TRY(check_ntt_args(tp, log_c, 2 * tp.p + 1, gen, "sharded RS needs 2^(log_n+1) >= 2 P^2",
+                         "generator order != 2n", gp));
+  return run_exchanges(
+      tp, 1, (16ull << (log_c - tp.p)) / tp.P, false, nullptr,
+      [&](uint32_t, fe* z) { return mlh_reed_solomon(ctx, dev_coeffs, log_n - tp.p, gp, z); },
+      [&](uint32_t, fe* recv) {
+        return mlh_shard_ntt_cross(ctx, recv, dev_code, log_c, tp.p, tp.rank, gen, 0);
+      });
 }
 
 }  // extern "C"
@@ -553,6 +508,10 @@ mlh_status mlh_sharded_reed_solomon(mlh_ctx* ctx, const mlh_transport* t, const 
 // ---------------------------------------------------------------------------
 namespace {
 
+// One committed layer.  Sharded (log_p > 0): block layout with block 2^log_s;
+// the rank holds the tree's lowest log_s levels over its own leaves and `top`,
+// the levels over every rank's level-log_s nodes.  Replicated (log_p = 0):
+// natural order, the whole tree local.
 struct SLayer {
   const fe* values = nullptr;
   uint8_t* tree = nullptr;
@@ -561,7 +520,12 @@ struct SLayer {
   uint8_t* top = nullptr;         // device tree over the gathered level-log_s nodes
   const uint8_t* root = nullptr;  // 32-byte device view of the root
   std::vector<uint8_t> top_host;  // host copy of `top` (query phase)
+  SLayer() = default;
+  SLayer(const fe* v, uint32_t n, uint32_t p, uint32_t s)
+      : values(v), log_n(n), log_p(p), log_s(p ? s : 0), sub_levels(p ? s : n - 1) {}
   uint64_t local_leaves() const { return 1ull << (log_n - 1 - log_p); }
+  // leaves of the top tree: every rank's level-sub_levels nodes (1 where replicated)
+  uint64_t top_leaves() const { return (local_leaves() >> sub_levels) << log_p; }
 };
 
 uint64_t level_offset(uint64_t leaves, uint32_t level) {
@@ -570,22 +534,28 @@ uint64_t level_offset(uint64_t leaves, uint32_t level) {
   return off;
 }
 
+// mlh_sharded_fri_prove in steps; mlh_sharded_commit_rs_code uses make_layer
+// and commit alone.
 struct ShardedFri {
   mlh_ctx* ctx;
   Tp& tp;
   Bufs& b;
   std::vector<SLayer> layers;
+  uint32_t n0 = 0, gather_log = 0;
+  // on the device: the transcript, the challenges r_0.. (one per layer), the
+  // last element, the RS flag
+  uint8_t* state = nullptr;
+  fe *rbuf = nullptr, *lastbuf = nullptr;
+  uint32_t* flagbuf = nullptr;
+  // read back: every layer's root, the last element; then the queries
+  std::vector<uint8_t> roots, mine;
+  uint8_t last[16];
+  std::vector<uint64_t> idx;
   ShardedFri(mlh_ctx* c, Tp& t, Bufs& bb) : ctx(c), tp(t), b(bb) {}
 
-  mlh_status make_layer(const fe* values, uint32_t log_n, bool sharded, SLayer* out) {
-    SLayer L;
-    L.values = values;
-    L.log_n = log_n;
-    L.log_p = sharded ? tp.p : 0;
-    L.log_s = sharded ? log_n - 2 * tp.p : 0;
-    L.sub_levels = sharded ? L.log_s : log_n - 1;
-    *out = L;
-    return MLH_OK;
+  // a freshly dealt layer (block 2^(log_n - 2 log P)) or a replicated one
+  SLayer make_layer(const fe* values, uint32_t log_n, bool sharded) const {
+    return SLayer(values, log_n, sharded ? tp.p : 0, log_n - 2 * tp.p);
   }
   mlh_status commit(SLayer& L) {  // local tree, then the top over all ranks
     MLH_TRY(b.get(mlh_merkle_layers_bytes(L.local_leaves()), &L.tree));
@@ -593,19 +563,18 @@ struct ShardedFri {
     return commit_top(L);
   }
   mlh_status commit_top(SLayer& L) {
-    const uint64_t tree_bytes = mlh_merkle_layers_bytes(L.local_leaves());
     if (L.log_p == 0) {
-      L.root = L.tree + tree_bytes - 32;
+      L.root = L.tree + mlh_merkle_layers_bytes(L.local_leaves()) - 32;
       return MLH_OK;
     }
-    const uint64_t half_t = L.local_leaves() >> L.sub_levels;
+    const uint64_t per_rank = L.top_leaves() >> L.log_p;
     const uint8_t* nodes = L.tree + 32 * level_offset(L.local_leaves(), L.sub_levels);
     uint8_t* gathered;
-    MLH_TRY(b.get(32 * half_t * tp.P, &gathered));
-    MLH_TRY(tp.all_gather(nodes, gathered, 32 * half_t));
-    MLH_TRY(b.get(mlh_merkle_layers_bytes(half_t * tp.P), &L.top));
-    MLH_TRY(mlh_merkle_top(ctx, gathered, tp.P, half_t, L.top));
-    L.root = L.top + mlh_merkle_layers_bytes(half_t * tp.P) - 32;
+    MLH_TRY(b.get(32 * L.top_leaves(), &gathered));
+    MLH_TRY(tp.all_gather(nodes, gathered, 32 * per_rank));
+    MLH_TRY(b.get(mlh_merkle_layers_bytes(L.top_leaves()), &L.top));
+    MLH_TRY(mlh_merkle_top(ctx, gathered, tp.P, per_rank, L.top));
+    L.root = L.top + mlh_merkle_layers_bytes(L.top_leaves()) - 32;
     return MLH_OK;
   }
   // block layout -> natural order on every rank (all-gather + one 2D copy per rank)
@@ -619,6 +588,171 @@ struct ShardedFri {
       HIP_TRY(ctx, hipMemcpy2DAsync(nat + r * S, tp.P * S * 16, g + r * local, S * 16, S * 16, T,
                                     hipMemcpyDeviceToDevice, ctx->stream));
     *out = nat;
+    return MLH_OK;
+  }
+  // the committed layer joins the proof: its root into the transcript, which
+  // draws the challenge of the fold that follows it
+  mlh_status push(const SLayer& L) {
+    layers.push_back(L);
+    return mlh_device_transcript_absorb(ctx, state, L.root, 32, rbuf + (layers.size() - 1));
+  }
+
+  // the device state and the codeword's own layer (gathered at or below gather_log)
+  mlh_status first_layer(const fe* code, uint32_t log_code, uint32_t gather, const mlh_transcript* tr) {
+    n0 = log_code;
+    gather_log = gather;
+    MLH_TRY(b.get(mlh_device_transcript_bytes(), &state));
+    MLH_TRY(b.get(16 * log_code, &rbuf));  // (log_code - 1 folds, one more root)
+    MLH_TRY(b.get(16, &lastbuf));
+    MLH_TRY(b.get(16, &flagbuf));
+    HIP_TRY(ctx, hipMemsetAsync(flagbuf, 0, 16, ctx->stream));
+    MLH_TRY(mlh_transcript_to_device(ctx, tr, state));
+    const bool sharded = log_code > gather_log;
+    fe* nat = nullptr;
+    if (!sharded) MLH_TRY(to_natural(code, log_code, &nat));
+    SLayer L0 = make_layer(sharded ? code : nat, log_code, sharded);
+    MLH_TRY(commit(L0));
+    return push(L0);
+  }
+
+  // Fold k of the newest layer with r_k.  The fold to two elements ends the
+  // commit phase (*done; fri/mod.rs:116-126); any other yields the next layer:
+  // replicated, or >= 2 local blocks, the folded pairs stay local, in the
+  // layout they had; else the folded layer is in natural block order and is
+  // re-dealt by an all-to-all or, at or below gather_log, gathered.
+  mlh_status fold_step(uint32_t k, bool* done) {
+    const SLayer& cur = layers.back();
+    const fe* r = rbuf + k;
+    const uint32_t log_next = cur.log_n - 1, log_local = cur.log_n - cur.log_p;
+    const uint32_t rank = cur.log_p ? tp.rank : 0;
+    const uint64_t next_local = 1ull << (log_next - cur.log_p);
+    fe* nv;
+    MLH_TRY(b.get(next_local * 16, &nv));
+    if (log_next == MLH_LOG_BLOWUP) {
+      MLH_TRY(mlh_shard_fri_fold_dr(ctx, cur.values, log_local, k, n0, r, nv, cur.log_s, cur.log_p, rank));
+      MLH_TRY(mlh_device_fri_last(ctx, nv, state, flagbuf, lastbuf));
+      *done = true;
+      return MLH_OK;
+    }
+    SLayer nx;
+    if (cur.log_p == 0 || log_next >= cur.log_p + cur.log_s + 1) {
+      nx = SLayer(nv, log_next, cur.log_p, cur.log_s);
+      MLH_TRY(b.get(mlh_merkle_layers_bytes(nx.local_leaves()), &nx.tree));
+      MLH_TRY(mlh_shard_fri_fold_commit_dr(ctx, cur.values, log_local, k, n0, r, nv, nx.tree, cur.log_s,
+                                           cur.log_p, rank));
+    } else {
+      MLH_TRY(mlh_shard_fri_fold_dr(ctx, cur.values, log_local, k, n0, r, nv, cur.log_s, cur.log_p, rank));
+      fe* dealt;
+      if (log_next > gather_log) {
+        MLH_TRY(b.get(next_local * 16, &dealt));
+        MLH_TRY(tp.all_to_all(nv, dealt, next_local / tp.P * 16));
+      } else {
+        MLH_TRY(b.get(next_local * tp.P * 16, &dealt));
+        MLH_TRY(tp.all_gather(nv, dealt, next_local * 16));
+      }
+      nx = make_layer(dealt, log_next, log_next > gather_log);
+      MLH_TRY(b.get(mlh_merkle_layers_bytes(nx.local_leaves()), &nx.tree));
+      MLH_TRY(mlh_merkle_commit_pairs(ctx, nx.values, nx.log_n - nx.log_p, nx.tree, nullptr));
+    }
+    MLH_TRY(commit_top(nx));
+    return push(nx);
+  }
+
+  // one wait: roots, challenges, last element, RS flag, the top trees; the
+  // host transcript replays them
+  mlh_status read_back(mlh_transcript* tr) {
+    const size_t nt = layers.size();
+    roots.resize(32 * nt);
+    for (size_t i = 0; i < nt; ++i)
+      HIP_TRY(ctx, hipMemcpyAsync(roots.data() + 32 * i, layers[i].root, 32, hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    uint32_t flag = 0;
+    std::vector<uint8_t> rhost(16 * nt);
+    HIP_TRY(ctx, hipMemcpyAsync(rhost.data(), rbuf, 16 * nt, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(last, lastbuf, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&flag, flagbuf, 4, hipMemcpyDeviceToHost, ctx->stream));
+    for (auto& L : layers)
+      if (L.top) {
+        L.top_host.resize(mlh_merkle_layers_bytes(L.top_leaves()));
+        HIP_TRY(ctx, hipMemcpyAsync(L.top_host.data(), L.top, L.top_host.size(), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+      }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (flag) return fail(ctx, MLH_ERR_NOT_RS_CODE, "not an RS code");
+    ReplayCheck rc(ctx, tr);  // root_i, then the challenge r_i the device drew from it
+    for (size_t i = 0; i < nt; ++i) {
+      rc.absorb(roots.data() + 32 * i, 32);
+      rc.expect(rhost.data() + 16 * i);
+    }
+    rc.absorb(last, 16);
+    return rc.status();
+  }
+
+  // queries (fri/mod.rs:266-277) into `mine`: per layer the owner of a pair
+  // opens it up its local levels; the top levels come from the host copy
+  mlh_status open_queries(mlh_transcript* tr) {
+    idx.resize(MLH_NUM_QUERIES);
+    transcript_draw_indices(tr, 1ull << (n0 - 1), MLH_NUM_QUERIES, idx.data());
+    const uint64_t qbytes = mlh_fri_query_bytes(n0);
+    mine.assign(qbytes * MLH_NUM_QUERIES, 0);
+    uint64_t layer_off = 0;
+    for (const SLayer& L : layers) {
+      const uint64_t leaves = 1ull << (L.log_n - 1);
+      std::vector<uint32_t> who;
+      std::vector<uint64_t> loc;
+      for (uint32_t q = 0; q < MLH_NUM_QUERIES; ++q) {
+        const uint64_t i = idx[q] % leaves;
+        if (L.log_p) {
+          const uint64_t r = (i >> L.log_s) & ((1ull << L.log_p) - 1);
+          if (r != tp.rank) continue;
+          loc.push_back(((i >> (L.log_s + L.log_p)) << L.log_s) | (i & ((1ull << L.log_s) - 1)));
+        } else {
+          loc.push_back(i);
+        }
+        who.push_back(q);
+      }
+      const uint64_t sub_rec = 32ull * (1 + L.sub_levels);
+      std::vector<uint8_t> recs(sub_rec * (loc.size() ? loc.size() : 1));
+      if (!loc.empty())
+        MLH_TRY(mlh_merkle_open_pairs(ctx, L.values, L.log_n - L.log_p, L.tree, L.sub_levels, loc.data(),
+                                      (uint32_t)loc.size(), recs.data()));
+      for (size_t w = 0; w < who.size(); ++w) {
+        const uint32_t q = who[w];
+        const uint64_t i = idx[q] % leaves;
+        uint8_t* dst = mine.data() + q * qbytes + layer_off;
+        memcpy(dst, recs.data() + w * sub_rec, sub_rec);
+        uint64_t off = 0, cnt = L.top_leaves();
+        for (uint32_t lv = 0; cnt > 1; ++lv, off += cnt, cnt >>= 1) {
+          const uint64_t node = (i >> (L.sub_levels + lv)) ^ 1;
+          memcpy(dst + sub_rec + 32 * lv, L.top_host.data() + 32 * (off + node), 32);
+        }
+      }
+      layer_off += 32ull * L.log_n;  // pair + (log_n - 1) siblings
+    }
+    return MLH_OK;
+  }
+
+  // every record is written by exactly one rank: OR of the gathered copies;
+  // then the proof's fields
+  mlh_status finish(mlh_transcript* tr, mlh_fri_proof* proof) {
+    uint8_t *dmine, *dall;
+    MLH_TRY(b.get(mine.size(), &dmine));
+    MLH_TRY(b.get(mine.size() * tp.P, &dall));
+    HIP_TRY(ctx, hipMemcpyAsync(dmine, mine.data(), mine.size(), hipMemcpyHostToDevice, ctx->stream));
+    MLH_TRY(tp.all_gather(dmine, dall, mine.size()));
+    std::vector<uint8_t> all(mine.size() * tp.P);
+    HIP_TRY(ctx, hipMemcpyAsync(all.data(), dall, all.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t r = 1; r < tp.P; ++r)
+      for (size_t i = 0; i < mine.size(); ++i) all[i] |= all[r * mine.size() + i];
+    proof->log_code = n0;
+    proof->num_trees = (uint32_t)layers.size();
+    proof->num_queries = MLH_NUM_QUERIES;
+    memcpy(proof->commitments, roots.data(), roots.size());
+    memcpy(proof->queries, all.data(), mine.size());
+    if (proof->query_indices) memcpy(proof->query_indices, idx.data(), 8 * MLH_NUM_QUERIES);
+    memcpy(proof->last_elem, last, 16);
+    mlh_transcript_random(tr, proof->last_random);
     return MLH_OK;
   }
 };
@@ -638,173 +772,15 @@ mlh_status mlh_sharded_fri_prove(mlh_ctx* ctx, const mlh_transport* t, const voi
   if (tp.p && log_code < 2 * tp.p) return fail(ctx, MLH_ERR_INVALID, "codeword too small for the world");
   if (tp.P == 1) return mlh_fri_prove(ctx, dev_code, log_code, tr, proof);
   if (gather_log < 2 * tp.p + 2) gather_log = 2 * tp.p + 2;
-  const uint32_t n0 = log_code, steps = log_code - MLH_LOG_BLOWUP;
   Bufs b(ctx);
   ShardedFri F(ctx, tp, b);
-  uint8_t* state;
-  fe *rbuf, *lastbuf;
-  uint32_t* flagbuf;
-  MLH_TRY(b.get(mlh_device_transcript_bytes(), &state));
-  MLH_TRY(b.get(16 * (steps + 1), &rbuf));
-  MLH_TRY(b.get(16, &lastbuf));
-  MLH_TRY(b.get(16, &flagbuf));
-  HIP_TRY(ctx, hipMemsetAsync(flagbuf, 0, 16, ctx->stream));
-  MLH_TRY(mlh_transcript_to_device(ctx, tr, state));
-  SLayer L0;
-  if (log_code > gather_log) {
-    MLH_TRY(F.make_layer(static_cast<const fe*>(dev_code), log_code, true, &L0));
-  } else {
-    fe* nat;
-    MLH_TRY(F.to_natural(static_cast<const fe*>(dev_code), log_code, &nat));
-    MLH_TRY(F.make_layer(nat, log_code, false, &L0));
-  }
-  MLH_TRY(F.commit(L0));
-  F.layers.push_back(L0);
-  MLH_TRY(mlh_device_transcript_absorb(ctx, state, F.layers.back().root, 32, rbuf));
+  MLH_TRY(F.first_layer(static_cast<const fe*>(dev_code), log_code, gather_log, tr));
   bool done = false;
-  for (uint32_t k = 0; k < steps; ++k) {
-    const SLayer cur = F.layers.back();
-    if ((1ull << cur.log_n) <= (1ull << MLH_LOG_BLOWUP)) break;
-    const fe* r = rbuf + k;
-    const uint32_t log_next = cur.log_n - 1;
-    const uint64_t next_local = 1ull << (log_next - cur.log_p);
-    fe* nv;
-    MLH_TRY(b.get(next_local * 16, &nv));
-    if ((1ull << log_next) == (1ull << MLH_LOG_BLOWUP)) {  // fri/mod.rs:116-126
-      MLH_TRY(mlh_shard_fri_fold_dr(ctx, cur.values, cur.log_n, k, n0, r, nv, 40, 0, 0));
-      MLH_TRY(mlh_device_fri_last(ctx, nv, state, flagbuf, lastbuf));
-      done = true;
-      break;
-    }
-    SLayer nx;
-    if (cur.log_p == 0) {
-      MLH_TRY(F.make_layer(nv, log_next, false, &nx));
-      MLH_TRY(b.get(mlh_merkle_layers_bytes(nx.local_leaves()), &nx.tree));
-      MLH_TRY(mlh_shard_fri_fold_commit_dr(ctx, cur.values, cur.log_n, k, n0, r, nv, nx.tree, 40, 0, 0));
-    } else if (log_next >= cur.log_p + cur.log_s + 1) {  // >= 2 local blocks: pairs stay local
-      nx.values = nv;
-      nx.log_n = log_next;
-      nx.log_p = cur.log_p;
-      nx.log_s = cur.log_s;
-      nx.sub_levels = cur.log_s;
-      MLH_TRY(b.get(mlh_merkle_layers_bytes(nx.local_leaves()), &nx.tree));
-      MLH_TRY(mlh_shard_fri_fold_commit_dr(ctx, cur.values, cur.log_n - cur.log_p, k, n0, r, nv,
-                                           nx.tree, cur.log_s, cur.log_p, tp.rank));
-    } else {  // the folded layer is in natural block order: re-deal or gather
-      MLH_TRY(mlh_shard_fri_fold_dr(ctx, cur.values, cur.log_n - cur.log_p, k, n0, r, nv, cur.log_s,
-                                    cur.log_p, tp.rank));
-      fe* dealt;
-      if (log_next > gather_log) {
-        MLH_TRY(b.get(next_local * 16, &dealt));
-        MLH_TRY(tp.all_to_all(nv, dealt, next_local / tp.P * 16));
-        MLH_TRY(F.make_layer(dealt, log_next, true, &nx));
-      } else {
-        MLH_TRY(b.get(next_local * tp.P * 16, &dealt));
-        MLH_TRY(tp.all_gather(nv, dealt, next_local * 16));
-        MLH_TRY(F.make_layer(dealt, log_next, false, &nx));
-      }
-      MLH_TRY(b.get(mlh_merkle_layers_bytes(nx.local_leaves()), &nx.tree));
-      MLH_TRY(mlh_merkle_commit_pairs(ctx, nx.values, nx.log_n - nx.log_p, nx.tree, nullptr));
-    }
-    MLH_TRY(F.commit_top(nx));
-    F.layers.push_back(nx);
-    MLH_TRY(mlh_device_transcript_absorb(ctx, state, F.layers.back().root, 32, rbuf + k + 1));
-  }
+  for (uint32_t k = 0; k + MLH_LOG_BLOWUP < log_code && !done; ++k) MLH_TRY(F.fold_step(k, &done));
   if (!done) return fail(ctx, MLH_ERR_INVALID, "fold produced no last element");
-
-  // one wait: roots, last element, RS flag; the host transcript replays them
-  const size_t nt = F.layers.size();
-  std::vector<uint8_t> roots(32 * nt);
-  for (size_t i = 0; i < nt; ++i)
-    HIP_TRY(ctx, hipMemcpyAsync(roots.data() + 32 * i, F.layers[i].root, 32, hipMemcpyDeviceToHost,
-                                ctx->stream));
-  uint8_t last[16];
-  uint32_t flag = 0;
-  std::vector<uint8_t> rhost(16 * nt);
-  HIP_TRY(ctx, hipMemcpyAsync(rhost.data(), rbuf, 16 * nt, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(last, lastbuf, 16, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&flag, flagbuf, 4, hipMemcpyDeviceToHost, ctx->stream));
-  for (auto& L : F.layers)
-    if (L.top) {
-      const uint64_t nb = mlh_merkle_layers_bytes(L.local_leaves() >> L.sub_levels << tp.p);
-      L.top_host.resize(nb);
-      HIP_TRY(ctx, hipMemcpyAsync(L.top_host.data(), L.top, nb, hipMemcpyDeviceToHost, ctx->stream));
-    }
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (flag) return fail(ctx, MLH_ERR_NOT_RS_CODE, "not an RS code");
-  {  // host replay: root_i, then the challenge r_i the device drew from it
-    ReplayCheck rc(ctx, tr);
-    for (size_t i = 0; i < nt; ++i) {
-      rc.absorb(roots.data() + 32 * i, 32);
-      rc.expect(rhost.data() + 16 * i);
-    }
-    rc.absorb(last, 16);
-    MLH_TRY(rc.status());
-  }
-
-  // queries (fri/mod.rs:266-277): the owner opens, records combined by a gather
-  const uint64_t half = 1ull << (log_code - 1);
-  std::vector<uint64_t> idx(MLH_NUM_QUERIES);
-  transcript_draw_indices(tr, half, MLH_NUM_QUERIES, idx.data());
-  const uint64_t qbytes = mlh_fri_query_bytes(log_code);
-  std::vector<uint8_t> mine(qbytes * MLH_NUM_QUERIES, 0);
-  uint64_t layer_off = 0;
-  for (const SLayer& L : F.layers) {
-    const uint64_t leaves = 1ull << (L.log_n - 1);
-    const uint64_t rec_len = 32ull * L.log_n;  // pair + (log_n - 1) siblings
-    std::vector<uint32_t> who;
-    std::vector<uint64_t> loc;
-    for (uint32_t q = 0; q < MLH_NUM_QUERIES; ++q) {
-      const uint64_t i = idx[q] % leaves;
-      if (L.log_p) {
-        const uint64_t r = (i >> L.log_s) & ((1ull << L.log_p) - 1);
-        if (r != tp.rank) continue;
-        loc.push_back(((i >> (L.log_s + L.log_p)) << L.log_s) | (i & ((1ull << L.log_s) - 1)));
-      } else {
-        loc.push_back(i);
-      }
-      who.push_back(q);
-    }
-    const uint64_t sub_rec = 32ull * (1 + L.sub_levels);
-    std::vector<uint8_t> recs(sub_rec * (loc.size() ? loc.size() : 1));
-    if (!loc.empty())
-      MLH_TRY(mlh_merkle_open_pairs(ctx, L.values, L.log_n - L.log_p, L.tree, L.sub_levels, loc.data(),
-                                    (uint32_t)loc.size(), recs.data()));
-    // host top levels of a sharded layer: leaves = P * half_t nodes
-    const uint64_t top_leaves = L.top ? (L.local_leaves() >> L.sub_levels) << tp.p : 0;
-    for (size_t w = 0; w < who.size(); ++w) {
-      const uint32_t q = who[w];
-      const uint64_t i = idx[q] % leaves;
-      uint8_t* dst = mine.data() + q * qbytes + layer_off;
-      memcpy(dst, recs.data() + w * sub_rec, sub_rec);
-      uint64_t off = 0, cnt = top_leaves;
-      for (uint32_t lv = 0; L.top && cnt > 1; ++lv, off += cnt, cnt >>= 1) {
-        const uint64_t node = (i >> (L.sub_levels + lv)) ^ 1;
-        memcpy(dst + sub_rec + 32 * lv, L.top_host.data() + 32 * (off + node), 32);
-      }
-    }
-    layer_off += rec_len;
-  }
-  // every record is written by exactly one rank: OR of the gathered copies
-  uint8_t *dmine, *dall;
-  MLH_TRY(b.get(mine.size(), &dmine));
-  MLH_TRY(b.get(mine.size() * tp.P, &dall));
-  HIP_TRY(ctx, hipMemcpyAsync(dmine, mine.data(), mine.size(), hipMemcpyHostToDevice, ctx->stream));
-  MLH_TRY(tp.all_gather(dmine, dall, mine.size()));
-  std::vector<uint8_t> all(mine.size() * tp.P);
-  HIP_TRY(ctx, hipMemcpyAsync(all.data(), dall, all.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  for (uint32_t r = 1; r < tp.P; ++r)
-    for (size_t i = 0; i < mine.size(); ++i) all[i] |= all[r * mine.size() + i];
-  proof->log_code = log_code;
-  proof->num_trees = (uint32_t)nt;
-  proof->num_queries = MLH_NUM_QUERIES;
-  memcpy(proof->commitments, roots.data(), 32 * nt);
-  memcpy(proof->queries, all.data(), mine.size());
-  if (proof->query_indices) memcpy(proof->query_indices, idx.data(), 8 * MLH_NUM_QUERIES);
-  memcpy(proof->last_elem, last, 16);
-  mlh_transcript_random(tr, proof->last_random);
-  return MLH_OK;
+  MLH_TRY(F.read_back(tr));
+  MLH_TRY(F.open_queries(tr));
+  return F.finish(tr, proof);
 }
 
 // commit_rs_code of a block-layout codeword: local leaves and subtrees, one
@@ -824,8 +800,7 @@ mlh_status mlh_sharded_commit_rs_code(mlh_ctx* ctx, const mlh_transport* t, cons
   if (log_code < 2 * tp.p + 1) return fail(ctx, MLH_ERR_INVALID, "codeword too small for the world");
   Bufs b(ctx);
   ShardedFri F(ctx, tp, b);
-  SLayer L;
-  MLH_TRY(F.make_layer(static_cast<const fe*>(dev_code), log_code, true, &L));
+  SLayer L = F.make_layer(static_cast<const fe*>(dev_code), log_code, true);
   MLH_TRY(F.commit(L));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned + kPinSlotB, L.root, 32, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -867,17 +842,10 @@ mlh_status mlh_sharded_sumcheck_prove(mlh_ctx* ctx, const mlh_transport* t, void
   if (n < tp.p) return fail(ctx, MLH_ERR_INVALID, "fewer variables than log2(world)");
   if (tp.P == 1) return mlh_sumcheck_prove(ctx, dev_m, dev_d, n, sum, tr, polys_out, rs_out);
   Bufs b(ctx);
-  uint8_t* state;
-  fe *prev, *polys, *rs, *sums, *pairs;
-  MLH_TRY(b.get(mlh_device_transcript_bytes(), &state));
-  MLH_TRY(b.get(16, &prev));
-  MLH_TRY(b.get(32ull * n, &polys));
-  MLH_TRY(b.get(16ull * n, &rs));
-  MLH_TRY(b.get(32, &sums));
-  MLH_TRY(b.get(32ull * tp.P, &pairs));
-  MLH_TRY(mlh_transcript_to_device(ctx, tr, state));
-  memcpy(ctx->pinned + kPinSlotA, sum, 16);
-  HIP_TRY(ctx, hipMemcpyAsync(prev, ctx->pinned + kPinSlotA, 16, hipMemcpyHostToDevice, ctx->stream));
+  RoundBuf rb(ctx, 2, n);  // extra: this rank's sums (2), the gathered pairs (2 P)
+  MLH_TRY(rb.alloc(32 + 32ull * tp.P));
+  fe *sums = rb.extra(), *pairs = sums + 2;
+  MLH_TRY(rb.seed(tr, sum));
   fe* m = static_cast<fe*>(dev_m);
   fe* d = static_cast<fe*>(dev_d);
   bool sharded = true;
@@ -904,16 +872,16 @@ mlh_status mlh_sharded_sumcheck_prove(mlh_ctx* ctx, const mlh_transport* t, void
       MLH_TRY(tp.all_gather(sums, pairs, 32));
       pr = pairs;
     }
-    MLH_TRY(mlh_device_sumcheck_round(ctx, pr, sharded ? tp.P : 1, prev, state, polys + 2 * k, rs + k));
+    MLH_TRY(mlh_device_sumcheck_round(ctx, pr, sharded ? tp.P : 1, rb.prev(), rb.dt(), rb.poly(k), rb.r(k)));
     if (k + 1 == n) {
-      MLH_TRY(mlh_sumcheck_fold_dr(ctx, m, d, log_local, rs + k));
+      MLH_TRY(mlh_sumcheck_fold_dr(ctx, m, d, log_local, rb.r(k)));
       break;
     }
     if (log_local >= 2) {
-      MLH_TRY(mlh_sumcheck_fold_sums_dr(ctx, m, d, log_local, rs + k, sums));
+      MLH_TRY(mlh_sumcheck_fold_sums_dr(ctx, m, d, log_local, rb.r(k), sums));
       --log_local;
     } else {  // sharded, local 2 -> 1 entries: gather the P-entry tables, go replicated
-      MLH_TRY(mlh_sumcheck_fold_dr(ctx, m, d, log_local, rs + k));
+      MLH_TRY(mlh_sumcheck_fold_dr(ctx, m, d, log_local, rb.r(k)));
       MLH_TRY(go_replicated(1));
       log_local = tp.p;
       MLH_TRY(mlh_sumcheck_sums_dev(ctx, m, d, log_local, sums));
@@ -925,18 +893,9 @@ mlh_status mlh_sharded_sumcheck_prove(mlh_ctx* ctx, const mlh_transport* t, void
     HIP_TRY(ctx, hipMemcpyAsync(dev_m, m, 16, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(dev_d, d, 16, hipMemcpyDeviceToDevice, ctx->stream));
   }
-  std::vector<uint8_t> host(48ull * n);
-  HIP_TRY(ctx, hipMemcpyAsync(host.data(), polys, 32ull * n, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(host.data() + 32ull * n, rs, 16ull * n, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ReplayCheck rc(ctx, tr);
-  for (uint32_t k = 0; k < n; ++k) {
-    rc.absorb(host.data() + 32 * k, 32);
-    rc.expect(host.data() + 32ull * n + 16 * k);
-  }
-  MLH_TRY(rc.status());
-  if (polys_out) memcpy(polys_out, host.data(), 32ull * n);
-  if (rs_out) memcpy(rs_out, host.data() + 32ull * n, 16ull * n);
+  MLH_TRY(rb.read_back());
+  MLH_TRY(rb.replay(tr));
+  rb.copy_out(polys_out, rs_out);
   return MLH_OK;
 }
 

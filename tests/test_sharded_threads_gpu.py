@@ -519,3 +519,147 @@ def test_config5_sharded_prove_production_shape(P):
         assert {19, 22, 25} <= set(redeals), redeals
     assert gather_log in gathers, sorted(gathers)
     assert max(lg for lg in redeals if lg < log_code) > gather_log
+
+
+# ---- one rank alone: the two modes of the sharded NTT batches, a failing exchange ----
+
+class _LoneRank:
+    """Rank 0 of a P = 2 world with no peers, on one thread: all_to_all copies
+    the caller's own chunk s into slot s of recv (all_gather: the whole send
+    buffer into every slot), device to device on the stream the library
+    passes.  Nothing waits on another thread.  The data is no real transform:
+    outputs are compared only between runs of this same emulation.
+    fail_at: the index of the all_to_all call that returns 1 and copies nothing."""
+
+    P = 2
+
+    def __init__(self, host_side, fail_at=None):
+        self.hip = _hip()
+        self.a2a_calls = 0
+
+        def copy(dst, src, n, stream):
+            assert self.hip.hipMemcpyAsync(dst, src, n, _D2D, stream) == 0
+
+        def a2a(user, send, recv, per, stream):
+            j = self.a2a_calls
+            self.a2a_calls += 1
+            if j == fail_at:
+                return 1
+            for s in range(self.P):
+                copy((recv or 0) + s * per, (send or 0) + s * per, per, stream)
+            return 0
+
+        def ag(user, send, recv, nbytes, stream):
+            for s in range(self.P):
+                copy((recv or 0) + s * nbytes, send, nbytes, stream)
+            return 0
+
+        self._fns = (_lib.ALL_TO_ALL_FN(a2a), _lib.ALL_GATHER_FN(ag))
+        self.transport = _lib.TransportC(self.P, 0, host_side, None, *self._fns)
+
+
+class _OwnContext:
+    """A fresh mlh_ctx on a stream of its own."""
+
+    def __enter__(self):
+        self.stream = torch.cuda.Stream()
+        h = ctypes.c_void_p()
+        DV.check(DV.lib().mlh_context_create(0, ctypes.c_void_p(self.stream.cuda_stream), ctypes.byref(h)))
+        self.ctx = h.value
+        return self.ctx
+
+    def __exit__(self, *exc):
+        torch.cuda.synchronize()
+        DV.lib().mlh_context_destroy(self.ctx)
+
+
+_LONE_LOG_N, _LONE_COUNT = 14, 3  # 2^13 local: the smallest the fused plan takes; both buffers reused
+_LONE = {}
+
+
+def _lone_inputs():
+    if "ins" not in _LONE:
+        _LONE["ins"] = [DV.random_limbs(1 << (_LONE_LOG_N - 1), seed=700 + i) for i in range(_LONE_COUNT)]
+    return _LONE["ins"]
+
+
+def _lone_call(ctx, world, entry, srcs):
+    """One batch call of `entry` ("fwd", "inv" or "fused") on device inputs
+    srcs; returns (status, output tensors, reported log_s or None)."""
+    L = DV.lib()
+    n = len(srcs)
+    outs = [DV.empty(srcs[0].shape[0]) for _ in range(n)]
+    pi = (ctypes.c_void_p * n)(*[s.data_ptr() for s in srcs])
+    po = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    g = DV.fe_bytes(_gen(_LONE_LOG_N))
+    torch.cuda.synchronize()
+    tp = ctypes.byref(world.transport)
+    if entry == "fused":
+        ls = ctypes.c_uint32(0xFFFF)
+        st = L.mlh_sharded_ntt_fused_batch(ctx, tp, pi, po, n, _LONE_LOG_N, g, ctypes.byref(ls))
+        return st, outs, ls.value
+    st = L.mlh_sharded_ntt_batch(ctx, tp, pi, po, n, _LONE_LOG_N, g, 1 if entry == "inv" else 0)
+    return st, outs, None
+
+
+def _lone_run(ctx, world, entry, srcs):
+    st, outs, ls = _lone_call(ctx, world, entry, srcs)
+    DV.check(st, ctx)
+    DV.check(DV.lib().mlh_synchronize(ctx), ctx)
+    return [DV.from_device(o) for o in outs], outs, ls
+
+
+def _lone_reference(entry):
+    """`entry`'s pipelined outputs on a fresh context, computed once."""
+    if entry not in _LONE:
+        with _OwnContext() as ctx:
+            ins = [DV.to_device(x) for x in _lone_inputs()]
+            _LONE[entry] = _lone_run(ctx, _LoneRank(0), entry, ins)[0]
+    return _LONE[entry]
+
+
+def test_ntt_batches_in_turn_and_pipelined_agree():
+    """mlh_sharded_ntt_batch (forward, then inverse of its outputs) and
+    mlh_sharded_ntt_fused_batch give byte-equal outputs, and the same log_s,
+    through a host-side transport (transforms in turn, one stream) and a
+    device-ordered one (three streams, count = 3: both buffer pairs reused)."""
+    got = {}
+    for host_side in (1, 0):
+        with _OwnContext() as ctx:
+            ins = [DV.to_device(x) for x in _lone_inputs()]
+            fwd, dfwd, _ = _lone_run(ctx, _LoneRank(host_side), "fwd", ins)
+            inv, _, _ = _lone_run(ctx, _LoneRank(host_side), "inv", dfwd)
+            fused, _, log_s = _lone_run(ctx, _LoneRank(host_side), "fused", ins)
+            got[host_side] = (fwd, inv, fused, log_s)
+    for what in range(3):
+        for i in range(_LONE_COUNT):
+            assert np.array_equal(got[1][what][i], got[0][what][i]), (what, i)
+    assert got[1][3] == got[0][3] and 3 <= got[0][3] < _LONE_LOG_N
+
+
+@pytest.mark.parametrize("entry", ["fwd", "fused"])
+@pytest.mark.parametrize("j", [0, 1, 2])
+def test_ntt_batch_failed_exchange_leaves_context_usable(entry, j):
+    """The transport's all_to_all returns 1 on its j-th call (a callback's
+    return value; no kernel misbehaves): the pipelined batch returns
+    MLH_ERR_COMM "transport all_to_all failed", mlh_synchronize succeeds, the
+    same call with a working callback equals a fresh context's output byte for
+    byte, and mlh_ntt at 2^12 on that context equals the C oracle."""
+    L = DV.lib()
+    want = _lone_reference(entry)
+    with _OwnContext() as ctx:
+        ins = [DV.to_device(x) for x in _lone_inputs()]
+        world = _LoneRank(0, fail_at=j)
+        st, _, _ = _lone_call(ctx, world, entry, ins)
+        assert st == _lib.MLH_ERR_COMM and world.a2a_calls == j + 1
+        assert L.mlh_last_error(ctx) == b"transport all_to_all failed"
+        assert L.mlh_synchronize(ctx) == _lib.MLH_OK
+        again = _lone_run(ctx, _LoneRank(0), entry, ins)[0]
+        for i in range(_LONE_COUNT):
+            assert np.array_equal(again[i], want[i]), i
+        x = DV.random_limbs(1 << 12, seed=77)
+        dx, out = DV.to_device(x), DV.empty(1 << 12)
+        torch.cuda.synchronize()
+        DV.check(L.mlh_ntt(ctx, DV.ptr(dx), DV.ptr(out), 12, DV.fe_bytes(_gen(12))), ctx)
+        DV.check(L.mlh_synchronize(ctx), ctx)
+        assert np.array_equal(DV.from_device(out), C.ntt(x, 12, _gen(12)))
