@@ -792,6 +792,81 @@ mlh_status mlh_system_verify_phased(const mlh_cs_program* prog, uint32_t log_hei
                                     const uint8_t sum[16], const uint8_t column_sum[16],
                                     const mlh_phased_proof* proof, mlh_transcript* tr);
 
+/* ---- phase 2 on the device: fill programs and the column sum --------------- *
+ * Between mlh_system_trace_randoms and mlh_trace_commit_range of the columns
+ * at and above P the prover fills "the columns that you must fill" after
+ * "knowing the value of the random challenges" (system.rs:23-26), e.g. u =
+ * 1 / (gamma - a) of a lookup, and then needs the sum of the sum columns
+ * (system.rs:27-29) for mlh_system_prove_phased.  Both run on the row-major
+ * matrix in place, with no transpose and no host copy of a column.
+ *
+ * A fill program is a per-row straight-line program whose outputs are written
+ * to columns of the same row: the constraint-program wire format above with
+ *   header   7 x u32: width, n_randoms, n_consts, n_temps, n_instr,
+ *            n_outputs, 0 (reserved)
+ *   consts   as above
+ *   code     as above, plus op 4 INV: temp[dst] = a^(M - 2), the inverse, zero
+ *            -> zero (field.rs:113-118), b = (0, 0)
+ *   outputs  n_outputs x 4 bytes: column, kind, index, 0: column `column` of
+ *            the row receives the operand (kind, index)
+ * and no degree.  Limits: those of constraint programs, n_outputs 1..width,
+ * output columns distinct and below width, at most 16 INV, and inverse depth
+ * 1: the operand of an INV may not depend on the result of an INV (a property
+ * of the value, tracked through every temp write).  mlh_fill_program_create
+ * returns MLH_ERR_INVALID for everything mlh_cs_program_create rejects
+ * (which still rejects op 4) and for a nonzero reserved header word, a
+ * duplicate or out-of-range output column, an INV with b != (0, 0), a 17th
+ * INV and an INV of a value that depends on an INV.
+ * Semantics: for every row, all column operands read the row as it stood when
+ * the call began, then the outputs are stored: an output column may be read
+ * (its old value is seen) and the columns that are no output are not written.
+ * A program object is host memory only and may be used with any context. */
+typedef struct mlh_fill_program mlh_fill_program;
+mlh_status mlh_fill_program_create(const uint8_t* bytes, uint64_t len, mlh_fill_program** out);
+void mlh_fill_program_destroy(mlh_fill_program* prog);
+uint32_t mlh_fill_program_width(const mlh_fill_program* prog);
+uint32_t mlh_fill_program_n_randoms(const mlh_fill_program* prog);
+uint32_t mlh_fill_program_n_outputs(const mlh_fill_program* prog);
+uint32_t mlh_fill_program_n_inverses(const mlh_fill_program* prog);
+uint32_t mlh_fill_program_output_mask(const mlh_fill_program* prog); /* bit j: column j is written */
+/* The host interpreter, the specification of mlh_trace_fill: out_row (width
+ * elements) = host_row (width canonical elements) after the fill.  Host only. */
+mlh_status mlh_fill_program_evaluate(const mlh_fill_program* prog, const uint8_t* host_row,
+                                     const uint8_t* host_randoms, uint8_t* out_row);
+/* The program on every row of the 2^log_height x width device matrix, in
+ * place (log_height 0..32).  width must equal the program's; host_randoms:
+ * n_randoms canonical elements, NULL allowed when 0.  One kernel launch on the
+ * context stream behind one copy of the randoms, constants and code; the call
+ * does not wait for the kernel.  A lane inverts once per INV for
+ * rows_per_thread of its rows (Montgomery's trick): 3 + 138 / rows_per_thread
+ * products per row and INV, the prefix products in a pooled scratch buffer of
+ * at most 64 MiB. */
+mlh_status mlh_trace_fill(mlh_ctx* ctx, const mlh_fill_program* prog, void* dev_matrix,
+                          uint32_t log_height, uint32_t width, const uint8_t* host_randoms);
+/* Its launch shape: threads per block (the largest of 256, 128, 64 whose
+ * width + n_temps + n_inverses LDS slots of 16 bytes fit 152 KiB), rows per
+ * thread and inversion (the largest of 16, 8, 4, 2, 1 that leaves 512 chunks;
+ * 1 without an INV) and blocks; a block visits ceil(ceil(2^log_height /
+ * (threads * rows_per_thread)) / blocks) chunks of threads * rows_per_thread
+ * rows. */
+mlh_status mlh_trace_fill_launch_info(const mlh_fill_program* prog, uint32_t log_height,
+                                      uint32_t* threads, uint32_t* rows_per_thread,
+                                      uint32_t* blocks);
+/* mlh_trace_fill under another launch shape, for measurements: threads 64, 128
+ * or 256, rows_per_thread a power of two up to 16 (1 for a program without
+ * INV); MLH_ERR_INVALID when (width + n_temps + n_inverses) * 16 * threads
+ * exceeds 152 KiB of LDS.  The same bytes as mlh_trace_fill. */
+mlh_status mlh_trace_fill_shaped(mlh_ctx* ctx, const mlh_fill_program* prog, void* dev_matrix,
+                                 uint32_t log_height, uint32_t width, const uint8_t* host_randoms,
+                                 uint32_t threads, uint32_t rows_per_thread);
+/* out = sum_i sum_{j in column_mask} matrix[i * width + j]: the column_sum of
+ * mlh_system_prove_phased ("the sum of all sum columns", system.rs:27-29).
+ * width 1..32, log_height 0..32; a mask bit at or above width is
+ * MLH_ERR_INVALID, mask 0 gives zero.  One streaming pass and a one-block
+ * reduction; synchronises once to return the value. */
+mlh_status mlh_trace_column_sum(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                uint32_t width, uint32_t column_mask, uint8_t out[16]);
+
 /* ---- multilinear PCS (src/fri/multilinear_pcs.rs) ------------------------ */
 typedef struct mlh_pcs_proof {
   mlh_fri_proof fri;

@@ -252,6 +252,19 @@ SIGNATURES = {
     "mlh_system_prove_phased": (_I, [_P, _P, _P, _P, _U32, _P, _P, _P, _P,
                                      ctypes.POINTER(PhasedProofC)]),
     "mlh_system_verify_phased": (_I, [_P, _U32, _U32, _U32, _P, _P, ctypes.POINTER(PhasedProofC), _P]),
+    "mlh_fill_program_create": (_I, [_P, _U64, ctypes.POINTER(_P)]),
+    "mlh_fill_program_destroy": (None, [_P]),
+    "mlh_fill_program_width": (_U32, [_P]),
+    "mlh_fill_program_n_randoms": (_U32, [_P]),
+    "mlh_fill_program_n_outputs": (_U32, [_P]),
+    "mlh_fill_program_n_inverses": (_U32, [_P]),
+    "mlh_fill_program_output_mask": (_U32, [_P]),
+    "mlh_fill_program_evaluate": (_I, [_P, _P, _P, _P]),
+    "mlh_trace_fill": (_I, [_P, _P, _P, _U32, _U32, _P]),
+    "mlh_trace_fill_launch_info": (_I, [_P, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32),
+                                        ctypes.POINTER(_U32)]),
+    "mlh_trace_fill_shaped": (_I, [_P, _P, _P, _U32, _U32, _P, _U32, _U32]),
+    "mlh_trace_column_sum": (_I, [_P, _P, _U32, _U32, _U32, _P]),
     "mlh_trace_columns_launch_info": (_I, [_U32, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     "mlh_trace_commit": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(_P)]),
     "mlh_trace_commitment_root": (_I, [_P, _P]),

@@ -14,8 +14,11 @@ proof a verifier checks without the trace (mlh_system_prove / _verify).
 ``WitnessLayout.pre_random_columns`` and ``sum_columns`` (system.rs:23-29) are
 the two-phase proof: ``System.phased_prover`` commits to the pre-random
 columns and hands out the trace randoms, the caller fills the other columns
-(``field_inv`` and the other field ops below), and ``prove`` /
-``PhasedSystemProof.verify`` are mlh_system_prove_phased / _verify_phased.
+(``PhasedProver.fill`` / ``Trace.fill``: a fill program, expressions with
+``inv``, run in place by mlh_trace_fill; or ``field_inv`` and the other field
+ops below on column vectors), and ``prove`` / ``PhasedSystemProof.verify`` are
+mlh_system_prove_phased / _verify_phased, the column sum by default from
+mlh_trace_column_sum.
 """
 import ctypes
 import struct
@@ -26,9 +29,10 @@ from .device import M, check, context, empty, fe_bytes, fe_from_bytes, lib, ptr
 from .polynomials import eq_table
 from .transcript import Transcript
 
-OP_ADD, OP_SUB, OP_MUL, OP_NEG = 0, 1, 2, 3
+OP_ADD, OP_SUB, OP_MUL, OP_NEG, OP_INV = 0, 1, 2, 3, 4
 COL, RAND, CONST, TEMP = 0, 1, 2, 3
 MAX_TEMPS = 32
+MAX_INVERSES = 16
 
 
 # ---- expressions -------------------------------------------------------------
@@ -86,6 +90,11 @@ def const(v):
     return Expr.wrap(int(v))
 
 
+def inv(e):
+    """1 / e, zero -> zero (field.rs:113-118); fill programs only."""
+    return Expr("inv", Expr.wrap(e))
+
+
 # ---- wire format -------------------------------------------------------------
 
 def encode_program(width, n_randoms, consts, n_temps, instrs, outs, degree):
@@ -102,26 +111,36 @@ def encode_program(width, n_randoms, consts, n_temps, instrs, outs, degree):
 
 
 _OPS = {"add": OP_ADD, "sub": OP_SUB, "mul": OP_MUL}
+_UNARY = {"neg": OP_NEG, "inv": OP_INV}
 
 
-def compile_program(exprs, width, n_randoms, degree):
-    """Expressions -> wire bytes.  Straight-line code in evaluation order; a
-    temp is released when its value has been consumed, the deeper operand of a
-    binary node is evaluated first, and equal constants share a pool entry."""
-    consts, instrs, free, live = [], [], [], [0]
-    need_memo = {}
+def _emit_outputs(exprs, allow_inv):
+    """Expressions -> (consts, n_temps, instrs, output operands): what
+    compile_program and compile_fill share.  Straight-line code in evaluation
+    order; a temp is released when its value has been consumed, the deeper
+    operand of a binary node is evaluated first, and equal constants share a
+    pool entry."""
+    consts, instrs, free, live, n_inv = [], [], [], [0], [0]
+    need_memo, inv_memo = {}, {}
 
     def need(e):  # temps needed to evaluate e (Sethi-Ullman)
         k = id(e)
         if k not in need_memo:
             if e.op in ("var", "rand", "const"):
                 need_memo[k] = 0
-            elif e.op == "neg":
+            elif e.op in _UNARY:
                 need_memo[k] = max(1, need(e.args[0]))
             else:
                 a, b = need(e.args[0]), need(e.args[1])
                 need_memo[k] = max(1, a + 1 if a == b else max(a, b))
         return need_memo[k]
+
+    def has_inv(e):
+        k = id(e)
+        if k not in inv_memo:
+            inv_memo[k] = e.op == "inv" or (e.op not in ("var", "rand", "const")
+                                            and any(has_inv(a) for a in e.args))
+        return inv_memo[k]
 
     def alloc():
         if free:
@@ -145,11 +164,19 @@ def compile_program(exprs, width, n_randoms, degree):
             if e.args[0] not in consts:
                 consts.append(e.args[0])
             return (CONST, consts.index(e.args[0]))
-        if e.op == "neg":
+        if e.op in _UNARY:
+            if e.op == "inv":
+                if not allow_inv:
+                    raise ValueError("a constraint program has no inverse (fill programs do)")
+                if has_inv(e.args[0]):
+                    raise ValueError("nested inverse: an inv() operand may not contain an inv()")
+                n_inv[0] += 1
+                if n_inv[0] > MAX_INVERSES:
+                    raise ValueError("fill program needs more than %d inverses" % MAX_INVERSES)
             a = emit(e.args[0])
             release(a)
             dst = alloc()
-            instrs.append((OP_NEG, dst, a, (0, 0)))
+            instrs.append((_UNARY[e.op], dst, a, (0, 0)))
             return (TEMP, dst)
         if need(e.args[1]) > need(e.args[0]):
             b = emit(e.args[1])
@@ -164,7 +191,67 @@ def compile_program(exprs, width, n_randoms, degree):
         return (TEMP, dst)
 
     outs = [emit(Expr.wrap(e)) for e in exprs]  # (an output's temp is never released)
-    return encode_program(width, n_randoms, consts, live[0], instrs, outs, degree)
+    return consts, live[0], instrs, outs
+
+
+def compile_program(exprs, width, n_randoms, degree):
+    """Expressions -> wire bytes of a constraint program (_emit_outputs).
+    ValueError for an ``inv`` node."""
+    consts, n_temps, instrs, outs = _emit_outputs(exprs, allow_inv=False)
+    return encode_program(width, n_randoms, consts, n_temps, instrs, outs, degree)
+
+
+def compile_fill(assignments, width, n_randoms):
+    """{column: Expr} -> wire bytes of a fill program (include/mlhip.h): the
+    code of compile_program with ``inv``, outputs in ascending column order.
+    ValueError for a nested inverse or more than 16 of them."""
+    cols = sorted(assignments)
+    for c in cols:
+        if not 0 <= c < width:
+            raise ValueError("output column %r outside the trace" % (c,))
+    consts, n_temps, instrs, outs = _emit_outputs([assignments[c] for c in cols], allow_inv=True)
+    b = struct.pack("<7I", width, n_randoms, len(consts), n_temps, len(instrs), len(outs), 0)
+    b += b"".join(int(c).to_bytes(16, "little") for c in consts)
+    for op, dst, a, bb in instrs:
+        b += bytes([op, dst, a[0], a[1], bb[0], bb[1], 0, 0])
+    for c, o in zip(cols, outs):
+        b += bytes([c, o[0], o[1], 0])
+    return b
+
+
+class FillProgram:
+    """A validated fill program (mlh_fill_program)."""
+
+    def __init__(self, wire):
+        self.wire = bytes(wire)
+        h = ctypes.c_void_p()
+        buf = (ctypes.c_uint8 * len(self.wire)).from_buffer_copy(self.wire)
+        check(lib().mlh_fill_program_create(buf, len(self.wire), ctypes.byref(h)))
+        self.h = h.value
+        self.width = lib().mlh_fill_program_width(self.h)
+        self.n_randoms = lib().mlh_fill_program_n_randoms(self.h)
+        self.n_outputs = lib().mlh_fill_program_n_outputs(self.h)
+        self.n_inverses = lib().mlh_fill_program_n_inverses(self.h)
+        self.output_mask = lib().mlh_fill_program_output_mask(self.h)
+
+    def __del__(self):
+        try:
+            lib().mlh_fill_program_destroy(self.h)
+        except Exception:
+            pass
+
+    def evaluate(self, row, randoms):
+        """The row after the fill, by the host interpreter."""
+        out = (ctypes.c_uint8 * (16 * self.width))()
+        check(lib().mlh_fill_program_evaluate(self.h, _elems(row), _elems(randoms), out))
+        return _split(out, self.width)
+
+    def launch_info(self, log_height):
+        """(threads per block, rows per thread and inversion, blocks)."""
+        t, k, b = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib().mlh_trace_fill_launch_info(self.h, log_height, ctypes.byref(t), ctypes.byref(k),
+                                               ctypes.byref(b)))
+        return t.value, k.value, b.value
 
 
 class Program:
@@ -268,6 +355,38 @@ class Trace:
         check(lib().mlh_trace_evaluate(ctx, ptr(self._matrix), self._height.bit_length() - 1,
                                        self._width, _elems(points), out), ctx)
         return _split(out, self._width)
+
+    def fill(self, program_or_assignments, randoms, device=0):
+        """Run a fill program on every row, in place (mlh_trace_fill): a
+        FillProgram, or {column: Expr} compiled for this width and randoms."""
+        prog = program_or_assignments
+        if not isinstance(prog, FillProgram):
+            prog = FillProgram(compile_fill(prog, self._width, len(randoms)))
+        if len(randoms) != prog.n_randoms:
+            raise ValueError("the fill program takes %d randoms" % prog.n_randoms)
+        ctx = context(device)
+        check(lib().mlh_trace_fill(ctx, prog.h, ptr(self._matrix), self._height.bit_length() - 1,
+                                   self._width, _elems(randoms)), ctx)
+        return prog
+
+
+def trace_column_sum(dev_matrix, width, columns, device=0):
+    """sum_i sum_{j in columns} matrix[i * width + j] (mlh_trace_column_sum):
+    the column_sum of a two-phase proof for columns = layout.sum_columns."""
+    n = dev_matrix.shape[0]
+    assert width >= 1 and n % width == 0
+    height = n // width
+    assert height & (height - 1) == 0 and height > 0
+    mask = 0
+    for j in columns:
+        if not 0 <= j < width:
+            raise ValueError("column %r outside the trace" % (j,))
+        mask |= 1 << j
+    ctx = context(device)
+    out = (ctypes.c_uint8 * 16)()
+    check(lib().mlh_trace_column_sum(ctx, ptr(dev_matrix), height.bit_length() - 1, width, mask,
+                                     out), ctx)
+    return fe_from_bytes(out)
 
 
 def trace_columns(dev_matrix, width, device=0, columns=None):
@@ -496,13 +615,30 @@ class PhasedProver:
     def commitment(self):
         return self._com1
 
-    def prove(self, transcript, total_sum, column_sum):
-        """mlh_system_prove_phased on a clone of the trace's matrix."""
+    def fill(self, assignments):
+        """Fill columns at and above pre_random_columns in place with
+        {column: Expr} over the row and ``self.randoms`` (mlh_trace_fill).  A
+        written column of commitment 1 would make the proof unprovable:
+        ValueError."""
+        lay = self._layout
+        prog = FillProgram(compile_fill(assignments, lay.columns, lay.randoms))
+        if prog.output_mask & ((1 << lay.pre_random_columns) - 1):
+            raise ValueError("fill writes a column below pre_random_columns (%d), which "
+                             "commitment 1 already holds" % lay.pre_random_columns)
+        return self._trace.fill(prog, self.randoms, self._device)
+
+    def prove(self, transcript, total_sum, column_sum=None):
+        """mlh_system_prove_phased on a clone of the trace's matrix.
+        column_sum = None: the sum of layout.sum_columns as the matrix stands
+        (mlh_trace_column_sum).  The value proved is kept in ``self.column_sum``."""
         if transcript.random() != self._entry:
             raise ValueError("prove needs the transcript in the state phased_prover was given")
         ctx = context(self._device)
         t, lay = self._trace, self._layout
         P, W = lay.pre_random_columns, lay.columns
+        if column_sum is None:
+            column_sum = trace_column_sum(t.matrix(), W, lay.sum_columns, self._device)
+        self.column_sum = column_sum
         com2 = Commitment.new(t, self._device, columns=(P, W - P)) if P < W else None
         p = PhasedSystemProof(self._com1.log_height, W, self._constraints.degree(), P, self._mask)
         work = t.matrix().clone()

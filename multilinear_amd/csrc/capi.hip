@@ -3,7 +3,8 @@
 //
 // Here: the context, the pool and the twiddle-table cache, the NTT /
 // Reed-Solomon / Merkle / field entries, the stepwise sumcheck entries, the
-// trace commitment, the constraint-system sumcheck and the system proofs.
+// trace commitment, the phase-2 fill and column sum, the constraint-system
+// sumcheck and the system proofs.
 // The FRI prover is fri_prover.hip; the sumcheck, PCS and batched-PCS provers
 // above it, pcs_prover.hip; the multi-GPU schedules, sharded.hip, and their
 // rank-local steps, shard_steps.hip; verifiers and host transcript, verify.cpp.
@@ -46,6 +47,7 @@
 #include "system_head.hpp"
 #include "tables.hpp"
 #include "trace_commit.hpp"
+#include "trace_fill.hpp"
 #include "transcript_dev.hpp"
 
 using namespace mlh;
@@ -1146,6 +1148,75 @@ void mlh_trace_commitment_destroy(mlh_trace_commitment* c) {
     (void)hipStreamSynchronize(c->ctx->stream);
     delete c;
   }
+}
+
+// ---- phase 2 of the two-phase proof: fill and column sum (trace_fill.hip) ----
+
+// The fill with an explicit launch shape (mlh_trace_fill: the shape of
+// fill_shape).  One pooled buffer holds this call's randoms beside the
+// program's constants, instruction words and output words, filled by one copy.
+mlh_status mlh_trace_fill_shaped(mlh_ctx* ctx, const mlh_fill_program* prog, void* dev_matrix,
+                                 uint32_t log_height, uint32_t width, const uint8_t* host_randoms,
+                                 uint32_t threads, uint32_t rows_per_thread) {
+  if (!ctx || !prog || !dev_matrix || width != prog->p.width || log_height > kCsMaxLogHeight ||
+      (prog->p.n_randoms && !host_randoms) || !fill_shape_ok(prog->p, threads, rows_per_thread))
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_fill: bad argument");
+  const FillProgram& p = prog->p;
+  std::vector<u128> rnd(p.n_randoms);
+  for (uint32_t i = 0; i < p.n_randoms; ++i)
+    if ((rnd[i] = h_load(host_randoms + 16ull * i)) >= kModulus)
+      return fail(ctx, MLH_ERR_INVALID, "non-canonical random");
+  const FillImageLayout l = fill_image_layout(p);
+  const std::vector<uint8_t> img = fill_build_image(p, rnd.data());
+  PoolBuf buf(ctx);
+  MLH_TRY(buf.alloc(img.size()));
+  HIP_TRY(ctx, hipMemcpyAsync(buf.p, img.data(), img.size(), hipMemcpyHostToDevice, ctx->stream));
+  const uint8_t* b = buf.as<uint8_t>();
+  FillDev dev{};
+  dev.uni = reinterpret_cast<const fe*>(b);
+  dev.code = reinterpret_cast<const uint32_t*>(b + l.code_off);
+  dev.outs = reinterpret_cast<const uint32_t*>(b + l.outs_off);
+  dev.width = p.width;
+  dev.n_temps = p.n_temps;
+  dev.n_instr = p.n_instr;
+  dev.n_pre = p.n_pre;
+  dev.n_inv = p.n_inv;
+  dev.n_outputs = p.n_outputs;
+  dev.K = rows_per_thread;
+  const uint64_t height = 1ull << log_height;
+  const uint32_t blocks = fill_blocks(p, fill_chunks(height, threads, dev.K), threads, dev.K);
+  PoolBuf prefix(ctx);  // the lanes' prefix products (trace_fill.hip)
+  if (const uint64_t elems = blocks * fill_prefix_elems(p, threads, dev.K)) {
+    MLH_TRY(prefix.alloc(16 * elems));
+    dev.prefix = prefix.as<fe>();
+  }
+  ProfScope ps(ctx, "trace_fill");
+  HIP_TRY(ctx, launch_trace_fill(dev, threads, blocks, reinterpret_cast<fe*>(dev_matrix), height,
+                                 ctx->stream));
+  ps.end();
+  return MLH_OK;  // (the buffer goes back to the pool: its next user is behind this launch on the stream)
+}
+
+mlh_status mlh_trace_fill(mlh_ctx* ctx, const mlh_fill_program* prog, void* dev_matrix,
+                          uint32_t log_height, uint32_t width, const uint8_t* host_randoms) {
+  uint32_t B = 0, K = 0;
+  if (prog && log_height <= kCsMaxLogHeight) fill_shape(prog->p, 1ull << log_height, &B, &K);
+  return mlh_trace_fill_shaped(ctx, prog, dev_matrix, log_height, width, host_randoms, B, K);
+}
+
+mlh_status mlh_trace_column_sum(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                uint32_t width, uint32_t column_mask, uint8_t out[16]) {
+  if (!ctx || !dev_matrix || !out || width < 1 || width > kCsMaxWidth ||
+      log_height > kCsMaxLogHeight || (width < 32 && (column_mask >> width)))
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_column_sum: bad argument");
+  ProfScope ps(ctx, "trace_column_sum");
+  HIP_TRY(ctx, launch_trace_column_sum(reinterpret_cast<const fe*>(dev_matrix), 1ull << log_height,
+                                       width, column_mask, ctx->partials, ctx->small, ctx->stream));
+  ps.end();
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, ctx->small, 16, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(out, ctx->pinned, 16);
+  return MLH_OK;
 }
 
 }  // extern "C"

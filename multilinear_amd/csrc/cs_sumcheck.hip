@@ -118,19 +118,7 @@ __device__ __forceinline__ void cs_linear(const CsDev& P, const fe* lane_lds, ui
     }
 }
 
-// *dst = the block's sum of v (red: 4 elements of LDS)
-__device__ __forceinline__ void cs_block_sum(fe v, uint32_t B, fe* red, fe* __restrict__ dst) {
-  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fe_add(v, shfl_xor_fe(v, m));
-  if (lane == 0) red[wid] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (uint32_t w = 1; w < (B >> 6); ++w) v = fe_add(v, red[w]);
-    fe_store(dst, v);
-  }
-  __syncthreads();
-}
+// (cs_block_sum: sc_dev.hpp)
 
 __device__ __forceinline__ void cs_zero_sums(const CsDev& P, fe* lane_lds, uint32_t B) {
   const uint32_t acc0 = 2 * P.width + P.n_temps;

@@ -20,6 +20,21 @@ __device__ __forceinline__ fe shfl_xor_fe(const fe& x, int mask) {
   return r;
 }
 
+// *dst = the sum of v over a block of B threads (red: 4 elements of LDS); the
+// constraint-system sums (cs_sumcheck.hip) and the column sum (trace_fill.hip)
+__device__ __forceinline__ void cs_block_sum(fe v, uint32_t B, fe* red, fe* __restrict__ dst) {
+  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = fe_add(v, shfl_xor_fe(v, m));
+  if (lane == 0) red[wid] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (uint32_t w = 1; w < (B >> 6); ++w) v = fe_add(v, red[w]);
+    fe_store(dst, v);
+  }
+  __syncthreads();
+}
+
 // Block reduction of two field sums; thread 0 ends with the totals.
 __device__ __forceinline__ void block_reduce2(fe& a, fe& b) {
   __shared__ fe sa[16], sb[16];  // up to 1024 threads

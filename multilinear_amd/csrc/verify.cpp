@@ -448,6 +448,54 @@ mlh_status mlh_cs_launch_info(const mlh_cs_program* prog, uint32_t log_height, u
   return MLH_OK;
 }
 
+// ---- fill programs (cs_program.hpp): decoder, accessors, host interpreter ----
+
+mlh_status mlh_fill_program_create(const uint8_t* bytes, uint64_t len, mlh_fill_program** out) {
+  if (!bytes || !out) return MLH_ERR_INVALID;
+  std::unique_ptr<mlh_fill_program> p(new mlh_fill_program());
+  if (!fill_decode(bytes, len, p->p)) return MLH_ERR_INVALID;
+  *out = p.release();
+  return MLH_OK;
+}
+void mlh_fill_program_destroy(mlh_fill_program* prog) { delete prog; }
+uint32_t mlh_fill_program_width(const mlh_fill_program* prog) { return prog ? prog->p.width : 0; }
+uint32_t mlh_fill_program_n_randoms(const mlh_fill_program* prog) {
+  return prog ? prog->p.n_randoms : 0;
+}
+uint32_t mlh_fill_program_n_outputs(const mlh_fill_program* prog) {
+  return prog ? prog->p.n_outputs : 0;
+}
+uint32_t mlh_fill_program_n_inverses(const mlh_fill_program* prog) {
+  return prog ? prog->p.n_inv : 0;
+}
+uint32_t mlh_fill_program_output_mask(const mlh_fill_program* prog) {
+  return prog ? prog->p.out_mask : 0;
+}
+
+mlh_status mlh_fill_program_evaluate(const mlh_fill_program* prog, const uint8_t* host_row,
+                                     const uint8_t* host_randoms, uint8_t* out_row) {
+  if (!prog || !host_row || !out_row || (prog->p.n_randoms && !host_randoms)) return MLH_ERR_INVALID;
+  std::vector<u128> v, r;
+  if (!load_canonical(host_row, prog->p.width, v) ||
+      !load_canonical(host_randoms, prog->p.n_randoms, r))
+    return MLH_ERR_INVALID;
+  u128 res[kCsMaxWidth];
+  fill_host_eval(prog->p, v.data(), r.data(), res);
+  for (uint32_t j = 0; j < prog->p.width; ++j) h_store(out_row + 16ull * j, res[j]);
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_fill_launch_info(const mlh_fill_program* prog, uint32_t log_height,
+                                      uint32_t* threads, uint32_t* rows_per_thread,
+                                      uint32_t* blocks) {
+  if (!prog || !threads || !rows_per_thread || !blocks || log_height > kCsMaxLogHeight)
+    return MLH_ERR_INVALID;
+  fill_shape(prog->p, 1ull << log_height, threads, rows_per_thread);
+  *blocks = fill_blocks(prog->p, fill_chunks(1ull << log_height, *threads, *rows_per_thread),
+                        *threads, *rows_per_thread);
+  return MLH_OK;
+}
+
 mlh_status mlh_system_challenges(mlh_transcript* tr, uint32_t log_rows, uint32_t n_randoms,
                                  uint32_t n_constraints, uint8_t* row_out, uint8_t* trace_out,
                                  uint8_t* constraint_out, uint8_t* mask_out) {
