@@ -365,7 +365,7 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
   // 3), so the 8 lanes of a row read the same entry: one row per thread is
   // loaded and shared through the idle exchange tile.  TB is stored EXPANDED
   // (the 4 limb-shifted multiples, as the stage twiddles), so its product is
-  // the 43-VALU expanded one (bfly_pp_v) instead of the 62-VALU full product.
+  // the 41-VALU expanded one (bfly_pp_v) instead of the 60-VALU full product.
   // MLH_P0_EARLY_TB: its loads (and the first TA pair's) are issued before the
   // last register phase, whose butterflies cover their latency; otherwise
   // just before the epilogue's barriers.

@@ -59,7 +59,7 @@ __device__ __forceinline__ void block_reduce2(fe& a, fe& b) {
 
 // Throughput form of the product for the HBM-streaming kernels: the
 // generated hand-scheduled 128x128 product + special-form fold (bfly_asm.hpp,
-// kind "f": any a < 2^128, canonical b; 62 VALU, no per-MAC pads) and one
+// kind "f": any a < 2^128, canonical b; 60 VALU, no per-MAC pads) and one
 // conditional subtraction back to canonical form.
 #ifndef MLH_SC_ASM_MUL
 #define MLH_SC_ASM_MUL 1

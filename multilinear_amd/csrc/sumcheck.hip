@@ -2095,7 +2095,7 @@ sumcheck_eq_tail_kernel(const fe* Tin, uint32_t Jin, const fe* __restrict__ rs_i
         if (n % 256 == 0) {
           // four lerps per lane per step, loads first (their LDS latency
           // overlaps), the products as generated butterflies with r expanded
-          // (u + r d, d = hi - lo: 60 VALU per pair half instead of ~100)
+          // (u + r d, d = hi - lo: 55 VALU per pair half instead of ~100)
           const fe two32 = fe{{0u, 1u, 0u, 0u}};
           const fe R1 = fe_mul_s(r, two32), R2 = fe_mul_s(R1, two32), R3 = fe_mul_s(R2, two32);
           for (uint32_t i0 = lane; i0 < n; i0 += 256) {

@@ -14,14 +14,40 @@ hazards covered by independent work, in the RELAXED representation:
 Butterfly (DIT): (u, v) -> (u + w*v, u - w*v), w given as its four limb-shifted
 multiples B_k = w * 2^(32k) mod M ("expanded" stage twiddles, fe_mul_pre):
   * product: 16 v_mad_u64_u32 column-scanned, carries counted by v_addc;
-    T = top bits (< 2^34) folded once: r + T*C, C = 2^128 - M = 0x2D00*2^32 - 1.
-    If r + T*C wraps 2^128 (probability ~2^-48) flag K (true t = s + C).
-  * a = u + t: carry -> + C; a second carry (only when the first sum's
-    remainder was >= 2^128 - C, probability ~2^-46) is flagged (C2).
-  * d = u - t: borrow -> - C; a second borrow is flagged (B2).
-  60 VALU per butterfly with a twiddle, 20 without, no s_nop in steady state.
+    T = top bits (< 2^34) folded once: s = r + x, x = T*C < 2^80,
+    C = 2^128 - M = 0x2D00*2^32 - 1.  x has three limbs, so only limbs 0..2
+    are added and limb 3 of s is r3 itself; the carry out of limb 2
+    (x2 < 2^16: probability ~2^-17) is flagged (E: true s = s + 2^96).
+  * a = u + s: a carry out of 2^128 (C1) is worth + C, a 46-bit constant,
+    which is added to limbs 0 and 1 only; limbs 2 and 3 of the first sum are
+    final.  The carry out of limb 1 (low64 + C >= 2^64: ~2^-18.5 for the
+    values a transform carries) is flagged (FA: true a = a + 2^64).
+  * d = u - s: borrow (B1) -> - C on limbs 0 and 1; the borrow out of limb 1
+    is flagged (FD: true d = d - 2^64).
+  55 VALU per butterfly with a twiddle (31 product, 5 fold, 3 s, 8 u +- s,
+  8 corrections), 16 without, no s_nop in the paired variants.
 The flags are SGPR lane masks; the C++ wrapper checks them with SALU ops and
-fixes flagged lanes on a cold path (each fix is +-C in relaxed arithmetic).
+fixes flagged lanes on a cold path that adds the lost ripples back in relaxed
+arithmetic: a += FA*2^64 + E*2^96, d -= FD*2^64 + E*2^96, where a wrap out of
+2^128 is worth +-C (and that C may wrap once more).  A flag set in a wave
+costs that wave one divergent branch: at 2^-17 per lane a few hundred waves
+per 2^24-point pass take it.  The fixes do not depend on how often the flags
+fire, only the time does.
+
+Products alone ('p': v <- w v by expanded multiples, any twiddle, 41 VALU;
+'f': v <- w v by a plain table entry, 60 VALU) keep the carry into limb 3,
+and their flag K is the carry out of 2^128 (true v = s + C).  In 'p' r3 sits
+in a physical register pair and needs an instruction to reach its operand
+whatever that instruction does; in 'f' the folded word reaches 2^93, so the
+carry out of limb 2 is not rare (about 1 lane in 100).  They save two
+instructions in the fold instead (fold_add_prog): the - T of
+T*C = (T*0x2D00 << 32) - T is taken from the sum's limbs 0 and 1 directly,
+and the borrow out of limb 1 (r1 < t_hi + 1: ~2^-30 in 'p', ~2^-20 in 'f')
+is flagged (G: true v = v - 2^64).
+
+A trivial butterfly reads u and v in both u + v and u - v, so the first of
+the two cannot overwrite either: limbs 2 and 3 of a leave the statement in
+write-only operands, which the wrapper assigns to u (a register rename).
 
 Precondition of the product (checked by tests/test_bfly_asm.py over every
 stage twiddle the NTT can use): the first mad of columns 1..3 adds
@@ -83,11 +109,29 @@ class Ins:
         return [self.sdst] if self.sdst and self.sdst != "junk" else []
 
 
-def product_prog(E, p, V, B, safe, kflag):
+def fold_add_prog(E, p, R, t_lo, t_hi, S, b):
+    """S = R + T*C for the products alone (kinds 'p', 'f'), seven instructions:
+    T*C = (T*0x2D00 << 32) - T, and the - T goes straight into R's limbs 0 and
+    1 instead of into a word of its own.  The borrow out of limb 1
+    (R1 < t_hi + 1: ~2^-30 in 'p', ~2^-20 in 'f') is left out and flagged
+    (G: true S = S - 2^64); K is the carry out of 2^128 (true S = S + C)."""
+    Y = ("pair", p + "Y.lo", p + "Y.hi")
+    E("mad", Y, [t_lo, "k2d00", 0], sdst="junk")
+    E("mad24", p + "Yh2", [t_hi, "k2d00", Y[2]])
+    E("sub", S[0], [R[0], t_lo], sdst=p + "bb5")
+    E("subb", p + "m1", [R[1], t_hi], sdst="G%d" % b, cin=p + "bb5")
+    E("add", S[1], [p + "m1", Y[1]], sdst=p + "e1")
+    E("addc", S[2], [R[2], p + "Yh2"], sdst=p + "e2", cin=p + "e1")
+    E("addc", S[3], [R[3], 0], sdst="K%d" % b, cin=p + "e2")
+
+
+def product_prog(E, p, V, B, safe):
     """t = sum_k V_k * B_k (relaxed), appended through E.  safe: count the carry
     of every column's first mad too (any twiddle); otherwise columns 1..3 rely
     on the stage-twiddle precondition (module docstring).  Returns the four
-    limb names of t; the wrap flag goes to SGPR kflag."""
+    limb names of r (the low four columns) and, with safe, the top word's
+    (t_lo, t_hi) unfolded; otherwise the folded top word is left in x0..x2.
+    The caller adds the two."""
     r = []
     acc = 0
     for j in range(4):
@@ -114,6 +158,8 @@ def product_prog(E, p, V, B, safe, kflag):
             acc = ("pair", nlo, nhi)
         else:
             t_lo, t_hi = acc[2], nhi
+    if safe:  # the product alone: the caller folds and adds in one go
+        return r, (t_lo, t_hi)
     # fold T*2^128 = T*C = T*0x2D00*2^32 - T
     Y = ("pair", p + "Y.lo", p + "Y.hi")
     E("mad", Y, [t_lo, "k2d00", 0], sdst="junk")
@@ -121,7 +167,7 @@ def product_prog(E, p, V, B, safe, kflag):
     E("sub", p + "x0", [0, t_lo], sdst=p + "bb0")
     E("subb", p + "x1", [Y[1], t_hi], sdst=p + "bb1", cin=p + "bb0")
     E("subb", p + "x2", [p + "Yh2", 0], sdst="junk", cin=p + "bb1")
-    return r, p
+    return r, None
 
 
 def fmul_prog(E, p, V, W):
@@ -130,9 +176,11 @@ def fmul_prog(E, p, V, W):
     scan over 7 columns (16 mads; the first mad of columns 0, 1 and the single
     mad of column 6 cannot overflow, every other carry is counted), then
     H*2^128 = H*C = H*0x2D00*2^32 - H: Z = L + (H*0x2D00 << 32) by 4 mads,
-    Z - H, and the top T < 2^47 folded once more (T*0x2D00*2^32 - T).  A
-    carry out of the last add (value >= 2^128, probability ~2^-35) is flagged
-    in K: the true value is s + C."""
+    Z - H (limbs x0..x3) with its top T = (tl, th) < 2^47, which the caller
+    folds once more (fold_add_prog).  That add keeps all four limbs: T*C
+    reaches 2^93 here, so the carry out of limb 2 is set in about one lane in
+    a hundred (measured with the emulator) and nearly every second wave would
+    take a cold path for it."""
     acc = 0
     r = []
     col_hi = {}
@@ -187,14 +235,7 @@ def fmul_prog(E, p, V, W):
     E("subb", p + "x3", [p + "a3", r[7]], sdst=p + "bb3", cin=p + "bb2")
     E("subb", p + "tl", [p + "a4", 0], sdst=p + "bb4", cin=p + "bb3")
     E("subb", p + "th", [p + "a5", 0], sdst="junk", cin=p + "bb4")
-    # fold T: T*C = (T*0x2D00) << 32 - T  (three limbs y0..y2, >= 0)
-    Y = ("pair", p + "Y.lo", p + "Y.hi")
-    E("mad", Y, [p + "tl", "k2d00", 0], sdst="junk")
-    E("mad24", p + "Yh2", [p + "th", "k2d00", Y[2]])
-    E("sub", p + "y0", [0, p + "tl"], sdst=p + "bb5")
-    E("subb", p + "y1", [Y[1], p + "th"], sdst=p + "bb6", cin=p + "bb5")
-    E("subb", p + "y2", [p + "Yh2", 0], sdst="junk", cin=p + "bb6")
-    return [p + "x0", p + "x1", p + "x2", p + "x3"], [p + "y0", p + "y1", p + "y2"]
+    return [p + "x0", p + "x1", p + "x2", p + "x3"], (p + "tl", p + "th")
 
 
 def canon_prog(E, p, b):
@@ -214,7 +255,7 @@ def bfly_prog(b, kind):
     trivial (w = 1), 'p': product only v <- w v (safe first mads; any twiddle).
     Operand names: u{b}_{i} (in, tied to a), v{b}_{i} (in, tied to d),
     B{b}_{k}{j} (twiddle limbs), kc1 (VGPR 0x2CFF), k2d00 (SGPR 0x2D00).
-    Flags K{b}, C2{b}, B2{b}."""
+    Flags E{b}, FA{b}, FD{b}; K{b}, G{b} for the products alone."""
     p = "b%d." % b
     U = ["u%d_%d" % (b, i) for i in range(4)]
     V = ["v%d_%d" % (b, i) for i in range(4)]
@@ -225,50 +266,49 @@ def bfly_prog(b, kind):
         return prog
     if kind == "f":
         W = ["W%d_%d" % (b, j) for j in range(4)]
-        X, Yl = fmul_prog(E, p, V, W)
-        S = ["d%d_%d" % (b, i) for i in range(4)]
-        E("add", S[0], [X[0], Yl[0]], sdst=p + "e0")
-        E("addc", S[1], [X[1], Yl[1]], sdst=p + "e1", cin=p + "e0")
-        E("addc", S[2], [X[2], Yl[2]], sdst=p + "e2", cin=p + "e1")
-        E("addc", S[3], [X[3], 0], sdst="K%d" % b, cin=p + "e2")
+        X, (tl, th) = fmul_prog(E, p, V, W)
+        fold_add_prog(E, p, X, tl, th, ["d%d_%d" % (b, i) for i in range(4)], b)
         return prog
     if kind in ("m", "p"):
         B = [["B%d_%d%d" % (b, k, j) for j in range(4)] for k in range(4)]
-        r, _ = product_prog(E, p, V, B, kind == "p", "K%d" % b)
-        if kind == "p":  # s = r + X written straight into v (tied output d)
-            S = ["d%d_%d" % (b, i) for i in range(4)]
-        else:
-            S = [p + "s%d" % i for i in range(4)]
+        r, T = product_prog(E, p, V, B, kind == "p")
+        if kind == "p":
+            # s = r + T*C written straight into v (tied output d).  r3 is the
+            # low half of a physical register pair, so limb 3 needs an
+            # instruction to reach its operand whatever it does: the add keeps
+            # its carry into limb 3 (K: the carry out of 2^128, ~2^-48)
+            fold_add_prog(E, p, r, T[0], T[1], ["d%d_%d" % (b, i) for i in range(4)], b)
+            return prog
+        # limb 3 of s is r3 itself; E: the carry that did not reach it
+        S = [p + "s%d" % i for i in range(3)] + [r[3]]
         E("add", S[0], [r[0], p + "x0"], sdst=p + "e0")
         E("addc", S[1], [r[1], p + "x1"], sdst=p + "e1", cin=p + "e0")
-        E("addc", S[2], [r[2], p + "x2"], sdst=p + "e2", cin=p + "e1")
-        E("addc", S[3], [r[3], 0], sdst="K%d" % b, cin=p + "e2")
-        if kind == "p":
-            return prog
+        E("addc", S[2], [r[2], p + "x2"], sdst="E%d" % b, cin=p + "e1")
     else:
         S = V
-    A = [p + "A%d" % i for i in range(4)]
-    D = [p + "D%d" % i for i in range(4)]
+    aout = ["a%d_%d" % (b, i) for i in range(4)]  # tied to U
+    dout = ["d%d_%d" % (b, i) for i in range(4)]  # tied to V
+    if kind == "t":
+        # u + v and u - v both read u and v, so whichever comes first cannot
+        # overwrite either: limbs 2 and 3 of a go to operands of their own
+        aout[2:] = ["x%d_%d" % (b, i) for i in (2, 3)]
+    # limbs 0 and 1 wait for the wrap correction; limbs 2 and 3 are final
+    A = [p + "A0", p + "A1", aout[2], aout[3]]
+    D = [p + "D0", p + "D1", dout[2], dout[3]]
     E("add", A[0], [U[0], S[0]], sdst=p + "f0")
     E("sub", D[0], [U[0], S[0]], sdst=p + "g0")
     for i in (1, 2, 3):
         E("addc", A[i], [U[i], S[i]], sdst=p + ("f%d" % i if i < 3 else "C1"), cin=p + "f%d" % (i - 1))
         E("subb", D[i], [U[i], S[i]], sdst=p + ("g%d" % i if i < 3 else "B1"), cin=p + "g%d" % (i - 1))
-    # a + C1*C, d - B1*C   (C = 0x2CFF_FFFFFFFF)
+    # a + C1*C, d - B1*C   (C = 0x2CFF_FFFFFFFF) on limbs 0 and 1 only
     E("cnd", p + "ma0", [0, -1], cin=p + "C1")
     E("cnd", p + "ma1", [0, "kc1"], cin=p + "C1")
     E("cnd", p + "md0", [0, -1], cin=p + "B1")
     E("cnd", p + "md1", [0, "kc1"], cin=p + "B1")
-    aout = ["a%d_%d" % (b, i) for i in range(4)]  # tied to U
-    dout = ["d%d_%d" % (b, i) for i in range(4)]  # tied to V
     E("add", aout[0], [A[0], p + "ma0"], sdst=p + "h0")
     E("sub", dout[0], [D[0], p + "md0"], sdst=p + "i0")
-    E("addc", aout[1], [A[1], p + "ma1"], sdst=p + "h1", cin=p + "h0")
-    E("subb", dout[1], [D[1], p + "md1"], sdst=p + "i1", cin=p + "i0")
-    E("addc", aout[2], [A[2], 0], sdst=p + "h2", cin=p + "h1")
-    E("subb", dout[2], [D[2], 0], sdst=p + "i2", cin=p + "i1")
-    E("addc", aout[3], [A[3], 0], sdst="C2%d" % b, cin=p + "h2")
-    E("subb", dout[3], [D[3], 0], sdst="B2%d" % b, cin=p + "i2")
+    E("addc", aout[1], [A[1], p + "ma1"], sdst="FA%d" % b, cin=p + "h0")
+    E("subb", dout[1], [D[1], p + "md1"], sdst="FD%d" % b, cin=p + "i0")
     return prog
 
 
@@ -442,7 +482,7 @@ def emit(kinds, bsrc):
     # trailing pad: the C++ code may read the flag SGPRs with a VALU right away
     tail = 0
     for back, it in enumerate(reversed(seq)):
-        if it is not None and any(s.startswith(("K", "C2", "B2")) for s in it.swrites()):
+        if it is not None and any(s.startswith(("K", "G", "E", "FA", "FD")) for s in it.swrites()):
             tail = max(tail, SGPR_GAP - 1 - back)
     return seq, assign, nv, ns, max(tail, 0)
 
@@ -452,17 +492,27 @@ def has_u(k):
 
 
 def operand_names(kinds):
+    """outs: tied in/out operands (u{b}_i, v{b}_i) and, for a trivial
+    butterfly, the write-only x{b}_2, x{b}_3 (limbs 2, 3 of a).  Its u limbs
+    2, 3 are only read but stay in/out operands: a plain input may be given
+    the register of another butterfly's in/out operand that holds the same
+    value (the zero-padded first pass copies u to v before its second stage),
+    and that butterfly overwrites it early."""
     outs, ins = [], []
     for b, k in enumerate(kinds):
         if has_u(k):
             outs += ["u%d_%d" % (b, i) for i in range(4)]
+        if k == "t":
+            outs += ["x%d_%d" % (b, i) for i in (2, 3)]
         outs += ["v%d_%d" % (b, i) for i in range(4)]
     flags = []
     for b, k in enumerate(kinds):
-        if k in ("m", "p", "f"):
-            flags.append("K%d" % b)
+        if k == "m":
+            flags.append("E%d" % b)
+        if k in ("p", "f"):
+            flags += ["K%d" % b, "G%d" % b]
         if has_u(k):
-            flags += ["C2%d" % b, "B2%d" % b]
+            flags += ["FA%d" % b, "FD%d" % b]
     for b, k in enumerate(kinds):
         if k in ("m", "p"):
             ins += ["B%d_%d%d" % (b, kk, j) for kk in range(4) for j in range(4)]
@@ -638,9 +688,9 @@ def value(l):
     return sum(v << (32 * i) for i, v in enumerate(l))
 
 
-def run_case(kinds, lines, opn, nv, uvals, vvals, wvals):
-    """Emulate one lane; apply the flag fixes as the C++ cold path does;
-    return [(a, d)] as integers (a = None for the one-operand kinds)."""
+def run_regs(kinds, lines, opn, uvals, vvals, wvals):
+    """Emulate one lane and return the register file: operand N is at '%N'
+    (opn maps operand names, flags included, to N)."""
     env = {}
     for b in range(len(kinds)):
         for i in range(4):
@@ -659,54 +709,84 @@ def run_case(kinds, lines, opn, nv, uvals, vvals, wvals):
         env["%%%d" % opn["kc1"]] = KC1
     if "k2d00" in opn:
         env["%%%d" % opn["k2d00"]] = K2D00
-    regs = emulate(lines, env)
+    return emulate(lines, env)
+
+
+def run_case(kinds, lines, opn, nv, uvals, vvals, wvals):
+    """Emulate one lane; apply the flag fixes as the C++ cold path does;
+    return [(a, d)] as integers (a = None for the one-operand kinds)."""
+    regs = run_regs(kinds, lines, opn, uvals, vvals, wvals)
     res = []
     for b in range(len(kinds)):
         d = value([regs["%%%d" % opn["v%d_%d" % (b, i)]] for i in range(4)])
-        if kinds[b] in ("p", "f"):  # v <- w v; flag K: true value s + C
-            res.append((None, add_c(d) if regs["%%%d" % opn["K%d" % b]] else d))
+        if kinds[b] in ("p", "f"):  # v <- w v; true value d + K 2^128 - G 2^64
+            d = relaxed_add(d, regs["%%%d" % opn["K%d" % b]] << 128)
+            res.append((None, relaxed_sub(d, regs["%%%d" % opn["G%d" % b]] << 64)))
             continue
         if kinds[b] == "c":
             res.append((None, d))
             continue
-        a = value([regs["%%%d" % opn["u%d_%d" % (b, i)]] for i in range(4)])
-        fk = regs.get("%%%d" % opn["K%d" % b], 0) if kinds[b] == "m" else 0
-        fc = regs["%%%d" % opn["C2%d" % b]]
-        fb = regs["%%%d" % opn["B2%d" % b]]
-        a, d = fix(a, d, fk, fc, fb)
+        hi = "x" if kinds[b] == "t" else "u"
+        a = value([regs["%%%d" % opn["%s%d_%d" % ("u" if i < 2 else hi, b, i)]] for i in range(4)])
+        fe = regs["%%%d" % opn["E%d" % b]] if kinds[b] == "m" else 0
+        fa = regs["%%%d" % opn["FA%d" % b]]
+        fd = regs["%%%d" % opn["FD%d" % b]]
+        a, d = fix(a, d, fe, fa, fd)
         res.append((a, d))
     return res
 
 
-def add_c(x):
-    x += C
-    if x >> 128:
-        x = (x & ((1 << 128) - 1)) + C
+def relaxed_add(x, y):
+    """x + y in the relaxed representation: a wrap out of 2^128 adds C, and a
+    second wrap adds C again."""
+    x += y
+    for _ in range(2):
+        if x >> 128:
+            x = (x & ((1 << 128) - 1)) + C
     return x
 
 
-def sub_c(x):
-    x -= C
-    if x < 0:
-        x = x + (1 << 128) - C
+def relaxed_sub(x, y):
+    """x - y in the relaxed representation: a borrow out of 2^128 subtracts C,
+    and a second borrow subtracts C again."""
+    x -= y
+    for _ in range(2):
+        if x < 0:
+            x = x + (1 << 128) - C
     return x
 
 
-def fix(a, d, fk, fc, fb):
-    """The cold path of the C++ wrapper (relaxed +-C fixes)."""
-    if fk:
-        a, d = add_c(a), sub_c(d)
-    if fc:
-        a = add_c(a)
-    if fb:
-        d = sub_c(d)
-    return a, d
+def fix(a, d, fe, fa, fd):
+    """The cold path of the C++ wrapper: the ripples the asm leaves out are
+    added back (fa: the carry out of limb 1 of a, fd: the borrow out of limb
+    1 of d, fe: the carry out of limb 2 of s = w v, which both a and d miss)."""
+    return relaxed_add(a, (fa << 64) + (fe << 96)), relaxed_sub(d, (fd << 64) + (fe << 96))
+
+
+def model(u, v, w=None):
+    """One butterfly as the asm computes it, on integers: (a, d, fe, fa, fd)
+    before the cold path; w = None is the trivial butterfly.  fix() of these
+    is exact mod M; the flags say which operands reach the cold path."""
+    m96, m64 = (1 << 96) - 1, (1 << 64) - 1
+    s, fe = v, 0
+    if w is not None:
+        P = sum(vk * (w * (1 << (32 * k)) % M) for k, vk in enumerate(limbs(v)))
+        r = P & ((1 << 128) - 1)
+        lo = (r & m96) + (P >> 128) * C
+        s, fe = (r & ~m96) | (lo & m96), lo >> 96
+    A, D = u + s, u - s
+    la = (A & m64) + (A >> 128) * C
+    ld = (D & m64) - (C if D < 0 else 0)
+    a = (A & ((1 << 128) - 1) & ~m64) | (la & m64)
+    d = (D & ((1 << 128) - 1) & ~m64) | (ld & m64)
+    return a, d, fe, la >> 64, 1 if ld < 0 else 0
 
 
 def selftest(kinds, lines, opn, nv, trials=3000, seed=1):
     rng = random.Random(seed)
     edge = [0, 1, M - 1, M, (1 << 128) - 1, C, C - 1, (1 << 128) - C, (1 << 128) - C - 1, M - C,
-            (1 << 127), (1 << 96) - 1, 0xFFFFFFFF, ((1 << 128) - 1) ^ 0xFFFFFFFF]
+            (1 << 127), (1 << 96) - 1, 0xFFFFFFFF, ((1 << 128) - 1) ^ 0xFFFFFFFF,
+            (1 << 64) - 1, (1 << 64) - C, (1 << 64) - C - 1, 1 << 96]
     # twiddles: roots of unity of small order (what the NTT uses) and random
     roots = []
     g = pow(3, (M - 1) >> 9, M)
@@ -776,6 +856,9 @@ def cxx_function(kinds, bsrc):
     body = []
     for f in flags:
         body.append("  uint64_t %s;" % f)
+    for o in outs:
+        if o[0] == "x":
+            body.append("  uint32_t %s;" % o)
     if ns:
         body.append("  uint64_t st[%d];" % ns)
     body.append("  uint64_t junk;")
@@ -787,7 +870,7 @@ def cxx_function(kinds, bsrc):
     ol = []
     for o in outs:
         b, i = o[1:].split("_")
-        ol.append('"+v"(%s%s.w[%s])' % (o[0], b, i))
+        ol.append('"=&v"(%s)' % o if o[0] == "x" else '"+v"(%s%s.w[%s])' % (o[0], b, i))
     for f in flags:
         ol.append('"=&s"(%s)' % f)
     for s in range(ns):
@@ -808,15 +891,19 @@ def cxx_function(kinds, bsrc):
     clob = ", ".join('"v%d"' % (VBASE + r) for r in range(nv))
     body.append('  asm volatile(\n      "%s"\n      : %s\n      : %s\n      : %s);' % (
         asm, ",\n        ".join(ol), ",\n        ".join(il), clob))
+    for o in outs:
+        if o[0] == "x":
+            b, i = o[1:].split("_")
+            body.append("  u%s.w[%s] = %s;" % (b, i, o))
     if flags:
         body.append("  rare = %s;" % " | ".join(flags))
         body.append("  if (__builtin_expect(rare != 0, 0)) {")
     for b in range(nb):
         if kinds[b] in ("p", "f"):
-            body.append("    if ((K%d >> __lane_id()) & 1u) v%d = relaxed_add_c(v%d);" % (b, b, b))
+            body.append("    prod_fix(v%d, K%d, G%d);" % (b, b, b))
         elif kinds[b] != "c":
-            fk = "K%d" % b if kinds[b] == "m" else "0ull"
-            body.append("    bfly_fix(u%d, v%d, %s, C2%d, B2%d);" % (b, b, fk, b, b))
+            fe = "E%d" % b if kinds[b] == "m" else "0ull"
+            body.append("    bfly_fix(u%d, v%d, %s, FA%d, FD%d);" % (b, b, fe, b, b))
     if flags:
         body.append("  }")
     stats = "%d VALU, %d s_nop, %d VGPR temps, %d SGPR-pair temps" % (
@@ -864,19 +951,48 @@ __device__ __forceinline__ fe relaxed_sub_c(const fe& x) {
   return t;
 }
 
-// Cold path: this lane's flags (K: the product wrapped, true t = s + C;
-// C2: a second carry in u + t; B2: a second borrow in u - t).
-__device__ __forceinline__ void bfly_fix_lane(fe& a, fe& d, uint32_t fk, uint32_t fc, uint32_t fb) {
-  if (fk) {
-    a = relaxed_add_c(a);
-    d = relaxed_sub_c(d);
-  }
-  if (fc) a = relaxed_add_c(a);
-  if (fb) d = relaxed_sub_c(d);
+// Relaxed x + y / x - y: a wrap out of 2^128 is worth C (2^128 = C mod M), and
+// adding or subtracting that C may wrap once more.
+__device__ __forceinline__ fe relaxed_add(const fe& x, const fe& y) {
+  fe t;
+  uint32_t k;
+  t.w[0] = addc(x.w[0], y.w[0], 0u, &k);
+  t.w[1] = addc(x.w[1], y.w[1], k, &k);
+  t.w[2] = addc(x.w[2], y.w[2], k, &k);
+  t.w[3] = addc(x.w[3], y.w[3], k, &k);
+  return k ? relaxed_add_c(t) : t;
 }
-__device__ __forceinline__ void bfly_fix(fe& a, fe& d, uint64_t fk, uint64_t fc, uint64_t fb) {
+__device__ __forceinline__ fe relaxed_sub(const fe& x, const fe& y) {
+  fe t;
+  uint32_t b;
+  t.w[0] = subb(x.w[0], y.w[0], 0u, &b);
+  t.w[1] = subb(x.w[1], y.w[1], b, &b);
+  t.w[2] = subb(x.w[2], y.w[2], b, &b);
+  t.w[3] = subb(x.w[3], y.w[3], b, &b);
+  return b ? relaxed_sub_c(t) : t;
+}
+
+// Cold path.  The butterflies leave out the carry ripples that are almost
+// never set and flag the lanes where one was: fa, the carry out of limb 1 of
+// a when it took its + C (true a = a + 2^64); fd, the borrow out of limb 1 of
+// d when it took its - C (true d = d - 2^64); fe, the carry out of limb 2 of
+// s = w v when the top word was folded in (true s = s + 2^96, which a gains
+// and d loses).
+__device__ __forceinline__ void bfly_fix_lane(fe& a, fe& d, uint32_t fe_, uint32_t fa, uint32_t fd) {
+  a = relaxed_add(a, fe{{0u, 0u, fa, fe_}});
+  d = relaxed_sub(d, fe{{0u, 0u, fd, fe_}});
+}
+__device__ __forceinline__ void bfly_fix(fe& a, fe& d, uint64_t fe_, uint64_t fa, uint64_t fd) {
   const uint32_t lane = __lane_id();
-  bfly_fix_lane(a, d, (uint32_t)(fk >> lane) & 1u, (uint32_t)(fc >> lane) & 1u, (uint32_t)(fb >> lane) & 1u);
+  bfly_fix_lane(a, d, (uint32_t)(fe_ >> lane) & 1u, (uint32_t)(fa >> lane) & 1u, (uint32_t)(fd >> lane) & 1u);
+}
+
+// Products alone (v <- w v): fk, the sum carried out of 2^128 (true v = v + C);
+// fg, the borrow out of limb 1 that the fold's - T left out (true v = v - 2^64).
+__device__ __forceinline__ void prod_fix(fe& v, uint64_t fk, uint64_t fg) {
+  const uint32_t lane = __lane_id();
+  if ((fk >> lane) & 1u) v = relaxed_add_c(v);
+  if ((fg >> lane) & 1u) v = relaxed_sub(v, fe{{0u, 0u, 1u, 0u}});
 }
 
 // Canonical representative of a relaxed value (x < 2^128 < 2M).

@@ -32,13 +32,12 @@ def cold_lines(lines):
         m = re.match(r"\s+s_cbranch_\w+\s+(\.LBB\w+)", l)
         if not m or m.group(1) not in label_at:
             continue
-        j = i + 1  # fall-through label
+        # fall-through label: the next one (the compiler may put the hot path's
+        # copies of the values the cold block redefines between the two)
+        j = i + 1
         while j < len(lines) and not re.match(r"\.LBB\w+:", lines[j]):
-            if re.match(r"\s+[vs]_", lines[j]):
-                j = None
-                break
             j += 1
-        if j is None or j >= len(lines):
+        if j >= len(lines):
             continue
         fall = re.match(r"(\.LBB\w+):", lines[j]).group(1)
         t = label_at[m.group(1)]

@@ -1,6 +1,8 @@
 """VALU-boundedness summary from one rocprofv3 pass with
 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE
---kernel-trace (dev tool) -> profiles/<tag>_valu.json.
+(dev tool) -> profiles/<tag>_valu.json.  Kernel durations come from the
+pass's kernel trace if it was taken with one, else from the dispatch
+timestamps of the counter rows (a counter pass of its own, no tracing).
 
 Per kernel (averaged over its dispatches):
   lane_instr_per_s = SQ_INSTS_VALU * 64 / kernel duration   (wave-instructions x 64 lanes)
@@ -27,7 +29,8 @@ def main():
     for r in csv.DictReader(open(os.path.join(d, "run_counter_collection.csv"))):
         ctr[r["Kernel_Name"]][r["Counter_Name"]].append((int(r["Dispatch_Id"]), float(r["Counter_Value"])))
     dur = {}
-    for r in csv.DictReader(open(os.path.join(d, "run_kernel_trace.csv"))):
+    trace = os.path.join(d, "run_kernel_trace.csv")
+    for r in csv.DictReader(open(trace if os.path.exists(trace) else os.path.join(d, "run_counter_collection.csv"))):
         dur[int(r["Dispatch_Id"])] = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-9
     out = {"round": tag, "log_n": 24, "nominal_lane_instr_per_s": NOMINAL, "kernels": {}}
     for name, cs in ctr.items():
