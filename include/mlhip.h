@@ -133,6 +133,11 @@ mlh_status mlh_ntt(mlh_ctx* ctx, const void* dev_coeffs, void* dev_evals, uint32
  * winter-math's inverse) and scales by 1/n.  Generators as mlh_ntt. */
 mlh_status mlh_intt(mlh_ctx* ctx, const void* dev_evals, void* dev_coeffs, uint32_t log_n,
                     const uint8_t gen[16]);
+/* mlh_ntt on 2^log_batch vectors of 2^log_n elements each, stored one after
+ * the other, in one launch per pass (gen of order exactly 2^log_n;
+ * log_n + log_batch <= 32).  In-place is allowed. */
+mlh_status mlh_ntt_batch(mlh_ctx* ctx, const void* dev_coeffs, void* dev_evals, uint32_t log_n,
+                         const uint8_t gen[16], uint32_t log_batch);
 /* bit_reverse_permutation (ntt/mod.rs:113-123), out of place (in != out);
  * log_n >= 1 (n = 1 panics in the reference: MLH_ERR_NOT_POW2). */
 mlh_status mlh_bit_reverse_permutation(mlh_ctx* ctx, const void* dev_in, void* dev_out,

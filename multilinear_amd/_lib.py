@@ -149,6 +149,7 @@ SIGNATURES = {
     "mlh_field_inv": (_I, [_P, _P, _P, _U64]),
     "mlh_ntt": (_I, [_P, _P, _P, _U32, _P]),
     "mlh_intt": (_I, [_P, _P, _P, _U32, _P]),
+    "mlh_ntt_batch": (_I, [_P, _P, _P, _U32, _P, _U32]),
     "mlh_bit_reverse_permutation": (_I, [_P, _P, _P, _U32]),
     "mlh_ntt_host": (_I, [_P, _P, _P, _U32, _P, _I]),
     "mlh_reed_solomon": (_I, [_P, _P, _U32, _P, _P]),

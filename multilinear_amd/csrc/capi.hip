@@ -159,6 +159,7 @@ static mlh_status get_ntt_tables(mlh_ctx* ctx, u128 gen, uint32_t log_n, bool in
     return MLH_OK;
   }
   tb->debug_sync = ctx->debug_sync;
+  tb->wide_offsets = ctx->ntt_wide_offsets;
   if (plan)
     ntt_plan_radices(log_n, &tb->nradix, tb->logr, plan, nplan);
   else
@@ -413,6 +414,8 @@ mlh_status mlh_context_create(int device, void* hip_stream, mlh_ctx** out) {
   c->stream = reinterpret_cast<hipStream_t>(hip_stream);
   const char* dbg = getenv("MLH_DEBUG_SYNC");
   c->debug_sync = dbg && *dbg && strcmp(dbg, "0") != 0;
+  const char* wide = getenv("MLH_NTT_WIDE_OFFSETS");
+  c->ntt_wide_offsets = wide && *wide && strcmp(wide, "0") != 0;
   void* st = nullptr;
   const bool ok = hipMalloc(&c->partials, 2 * kMaxRedBlocks * sizeof(fe)) == hipSuccess &&
                   hipMalloc(&c->small, 64 * sizeof(fe)) == hipSuccess &&
@@ -634,6 +637,29 @@ mlh_status mlh_ntt(mlh_ctx* ctx, const void* dev_coeffs, void* dev_evals, uint32
 mlh_status mlh_intt(mlh_ctx* ctx, const void* dev_evals, void* dev_coeffs, uint32_t log_n,
                     const uint8_t gen[16]) {
   return ntt_entry(ctx, dev_evals, dev_coeffs, log_n, gen, true);
+}
+
+mlh_status mlh_ntt_batch(mlh_ctx* ctx, const void* dev_coeffs, void* dev_evals, uint32_t log_n,
+                         const uint8_t gen[16], uint32_t log_batch) {
+  if (!ctx || !dev_coeffs || !dev_evals || !gen) return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (log_n < 1 || log_n > 32 || log_n + log_batch > 32)
+    return fail(ctx, MLH_ERR_NOT_POW2, "The number of coeffs must be a power of 2 (n >= 2)");
+  const u128 g = h_load(gen);
+  if (g >= kModulus || !check_generator(g, log_n))
+    return fail(ctx, MLH_ERR_BAD_GENERATOR, "generator not of order 2^log_n");
+  const fe* in = reinterpret_cast<const fe*>(dev_coeffs);
+  fe* out = reinterpret_cast<fe*>(dev_evals);
+  NttTables tb;
+  MLH_TRY(get_ntt_tables(ctx, g, log_n, false, &tb));
+  const uint64_t batch = 1ull << log_batch;
+  if (log_n <= 10) {
+    HIP_TRY(ctx, launch_ntt_small(in, out, tb.tw_small, log_n, 1ull << log_n, tb.scale, false,
+                                  ctx->stream, batch));
+    return MLH_OK;
+  }
+  MLH_TRY(ensure_ntt_scratch(ctx, log_n + log_batch));
+  HIP_TRY(ctx, launch_ntt_passes(in, out, ctx->ntt_scratch, tb, log_n, 0, ctx->stream, nullptr, batch));
+  return MLH_OK;
 }
 
 static mlh_status vec_op(mlh_ctx* ctx, int op, const void* a, const void* b, void* out, uint64_t n) {

@@ -79,6 +79,9 @@ struct mlh_ctx {
   // debug / test hooks, fixed at creation (MLH_DEBUG_SYNC) or set through the
   // API (mlh_set_ntt_plan): never read from the environment on a hot path
   bool debug_sync = false;
+  // MLH_NTT_WIDE_OFFSETS: every NTT pass takes the 64-bit-offset kernels (the
+  // path of tiles spanning 2^32 bytes and more), so tests reach it at small N
+  bool ntt_wide_offsets = false;
   uint32_t forced_plan[kMaxPasses] = {0};
   uint32_t forced_plan_len = 0;
   // kernel timer (mlh_profile_*): HIP events on the launch stream

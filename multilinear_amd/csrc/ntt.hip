@@ -25,6 +25,10 @@
 //     read from a per-workgroup LDS copy;
 //   * the last pass tiles 8 consecutive k_1 values so its scattered natural-
 //     order stores are still 128-byte runs.
+//   * every global address is a wave-uniform base (SGPR pair) plus one 32-bit
+//     per-lane byte offset per buffer; a thread's 8 rows differ by compile-time
+//     constants that go to the base (64-bit offsets, ntt_pass_wide_kernel,
+//     where a tile spans 2^32 bytes).
 // Sizes N <= 2^10 use one LDS-resident workgroup (ntt_small).
 #include <stdio.h>
 #include <stdlib.h>
@@ -43,6 +47,67 @@ constexpr int kEPT = 8;   // elements per thread
 
 __device__ __forceinline__ uint32_t bitrev(uint32_t x, int bits) {
   return __builtin_bitreverse32(x) >> (32 - bits);
+}
+
+// Global accesses of the pass kernels: a wave-uniform pointer (SGPR pair) plus
+// a per-lane byte offset.  With a 32-bit offset the compiler selects the
+// "global_load v, v_off32, s[base:base+1]" form, so the per-lane part of an
+// address is one VGPR formed once and every further term (the element's
+// compile-time row, the tile, the vector) is added to the base on the SALU.
+// Off = uint32_t is valid while every byte offset from the uniform base is
+// below 2^32 (the host decides per launch: pass_wide()); Off = uint64_t is
+// the same arithmetic in 64 bits.
+// The narrow form passes the base through readfirstlane (a scalar move for a
+// value that is uniform already): otherwise the optimiser reassociates
+// (base + constant row) + lane into (base + lane) + constant row, a 64-bit
+// VGPR address plus one v_lshl_add_u64 per access.
+// (the rebuilt pointer is typed as global memory, which an integer round trip
+// would otherwise forget)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) u32x4 global_u32x4;
+template <typename Off>
+__device__ __forceinline__ global_u32x4* pass_addr(const void* ubase, Off lane_bytes) {
+  uint64_t v = reinterpret_cast<uint64_t>(ubase);
+  if constexpr (sizeof(Off) == 4) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    v = ((uint64_t)hi << 32) | lo;
+  }
+  return (global_u32x4*)(v + lane_bytes);
+}
+template <typename Off>
+__device__ __forceinline__ fe fe_load_at(const fe* ubase, Off lane_bytes) {
+  const u32x4 v = *pass_addr<Off>(ubase, lane_bytes);
+  return fe{{v.x, v.y, v.z, v.w}};
+}
+template <typename Off>
+__device__ __forceinline__ void fe_store_at(fe* ubase, Off lane_bytes, const fe& x) {
+  *pass_addr<Off>(ubase, lane_bytes) = u32x4{x.w[0], x.w[1], x.w[2], x.w[3]};
+}
+// Instruction selection sees one basic block at a time, and takes the
+// SGPR-base form only where the 32-bit lane offset's zero extension is in the
+// access's own block; the butterflies' rare-case branches split the epilogue
+// into many blocks, and the optimiser keeps one shared (hoisted) extension.
+// An empty statement that redefines the offset in place (same register, no
+// instruction) before a block's accesses keeps each extension local.
+__device__ __forceinline__ void pin_lane_offset(uint32_t& v) { asm("" : "+v"(v)); }
+__device__ __forceinline__ void pin_lane_offset(uint64_t&) {}
+constexpr uint32_t bitrev_c(uint32_t x, int bits) {
+  uint32_t r = 0;
+  for (int i = 0; i < bits; ++i) r |= ((x >> i) & 1u) << (bits - 1 - i);
+  return r;
+}
+// Position of a thread's elements in register phase (s0, q): the group index
+// gamma = t * G + gi keeps its low s0 bits and moves the rest up by q;
+// element i of the group adds i << s0.  A bit placement, so it splits into a
+// per-lane part (of t * G) and a compile-time part (of gi and i) on disjoint
+// bits: pos = pos_lane + pos_c, and every address linear in pos is one lane
+// term plus a constant.
+constexpr uint32_t phase_bpos(uint32_t gamma, int s0, int q) {
+  return (gamma & ((1u << s0) - 1u)) | ((gamma >> s0) << (s0 + q));
+}
+constexpr uint32_t phase_pos_c(int s0, int q, int e) {
+  return phase_bpos((uint32_t)(e >> q), s0, q) + ((uint32_t)(e & ((1 << q) - 1)) << s0);
 }
 
 struct PassGeom {
@@ -123,16 +188,19 @@ constexpr int pass_waves_per_simd(int logr, int ept) {
 // folded into pass 0's loads; pass 0 only, never the last pass).
 // EPT: elements per thread (8: register phases of 3 stages; 16: of 4 stages,
 // one LDS exchange fewer at R = 2^8, twice the VGPRs).
-template <int LOGR, int TW, int ZT, int EPT = kEPT>
-__global__ void __launch_bounds__(kCols * (1 << LOGR) / EPT,
-                                  (TW == 2 || TW == 4) ? 1 : pass_waves_per_simd(LOGR, EPT))
-ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
-                const fe* __restrict__ ta, const fe* __restrict__ tb, PassGeom g) {
+// WIDE: 64-bit per-lane offsets (a tile or table that spans 2^32 bytes or more).
+// (the body of both kernels below: ntt_pass_kernel is the narrow form,
+// ntt_pass_wide_kernel the wide one)
+template <int LOGR, int TW, int ZT, int EPT, bool WIDE>
+__device__ __forceinline__ void ntt_pass_body(const fe* in, fe* out, const fe* __restrict__ tw,
+                                              const fe* __restrict__ ta, const fe* __restrict__ tb,
+                                              const PassGeom& g) {
   constexpr int R = 1 << LOGR;
   constexpr int LQ = EPT == 16 ? 4 : 3;  // stages per register phase
   constexpr int TPC = R / EPT;  // threads per column
   constexpr bool LAST = TW == 2 || TW == 4;
   constexpr bool SH = TW == 4;
+  using Off = std::conditional_t<WIDE, uint64_t, uint32_t>;
   // sharded last pass: global storage index -> receive-buffer position
   auto phys = [&](uint64_t v) -> uint64_t {
     if constexpr (SH)
@@ -182,14 +250,17 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
   out += vec << g.lout_v;
 
   // ---- tile geometry -----------------------------------------------------
-  uint64_t base, jrest = 0, k1 = 0, mid = 0;
+  // (base, jcol0, k1u, mid are wave-uniform; the lane's column cB is added
+  // where an address or index needs it)
+  uint64_t base, jcol0 = 0, jrest = 0, k1u = 0, mid = 0;
   uint32_t rshift;  // log2 element stride between rows of this digit
   uint32_t cshift;  // log2 element stride between the 8 columns
   if (!LAST) {
     const uint32_t lw = g.lstride;  // W >= kCols
     const uint64_t hi = tile >> (lw - kLogCols), lo = tile & ((1ull << (lw - kLogCols)) - 1);
     base = (hi << (LOGR + lw)) + (lo << kLogCols);
-    jrest = (lo << kLogCols) + cB;
+    jcol0 = lo << kLogCols;
+    jrest = jcol0 + cB;
     rshift = lw;
     cshift = 0;
   } else {
@@ -198,12 +269,15 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
     const uint64_t d1hi = tile >> lmid;
     mid = tile & ((1ull << lmid) - 1);
     base = (d1hi << (kLogCols + lw1)) + (mid << LOGR);
-    k1 = (d1hi << kLogCols) + cB;
+    k1u = d1hi << kLogCols;
     rshift = 0;
     cshift = lw1;
   }
-  const fe* src = in + base + ((uint64_t)c << cshift);  // phase 1's column
-  fe* dst = out + base + ((uint64_t)cB << cshift);
+  const fe* tile_in = in + base;
+  fe* tile_out = out + base;
+  // phase 1's rows are bitrev(t EPT + e) = bitrev(t EPT) + bitrev(e): the lane's
+  // byte offset into the tile, and a compile-time row added to the base
+  const Off ld_lane = ((((Off)bitrev((uint32_t)t * EPT, LOGR)) << rshift) + ((Off)c << cshift)) << 4;
 
 
   // ---- phase 1: load bit-reversed rows, stages 0..2 in registers ---------
@@ -236,7 +310,18 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
         row = ((((q0 << 3) + (l & 7)) << g.sh_p)) | src;
       }
       const uint32_t col = l >> 3;
-      lds[row * kCols + (col ^ swz(row))] = fe_load(in + phys(base + ((uint64_t)col << cshift) + row));
+      if constexpr (SH) {
+        lds[row * kCols + (col ^ swz(row))] = fe_load(in + phys(base + ((uint64_t)col << cshift) + row));
+      } else {
+        // idx = e NT + tid on disjoint bits, and (col << cshift) + row places
+        // idx's bits: the element offset of idx is that of e NT (uniform)
+        // plus that of tid (lane)
+        auto tile_at = [&](uint32_t i) -> Off {
+          return ((Off)((i & 63) >> 3) << cshift) + (Off)((i >> 6) * 8 + (i & 7));
+        };
+        lds[row * kCols + (col ^ swz(row))] =
+            fe_load_at<Off>(tile_in + (uint64_t)tile_at((uint32_t)(e * NT)), tile_at((uint32_t)tid) << 4);
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -256,13 +341,16 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
       // coefficient row*W + col, row < R/2, lives at bitrev(col)*(R/2) +
       // bitrev_{LOGR-1}(row) = bitrev(col)*(R/2) + (t*EPT + e)/2: each lane
       // reads 4 consecutive elements
+      // (bitrev(col) = bitrev(jcol0) + bitrev_3(cB) << (logw - 3): uniform + lane)
       const uint32_t logw = g.log_n - LOGR;
-      const uint64_t colr = __builtin_bitreverse64(jrest) >> (64 - logw);
-      x[e] = fe_load(in + (colr << (LOGR - 1)) + ((uint32_t)(t * EPT + e) >> 1));
+      const uint64_t colr_u = __builtin_bitreverse64(jcol0) >> (64 - logw);
+      const Off colr_l = (Off)bitrev((uint32_t)cB, kLogCols) << (logw - kLogCols);
+      x[e] = fe_load_at<Off>(in + (colr_u << (LOGR - 1)) + (e >> 1),
+                             ((colr_l << (LOGR - 1)) + (Off)(t * (EPT / 2))) << 4);
     } else if constexpr (SH) {
       x[e] = fe_load(in + phys(base + ((uint64_t)c << cshift) + ((uint64_t)row << rshift)));
     } else {
-      x[e] = fe_load(src + ((uint64_t)row << rshift));
+      x[e] = fe_load_at<Off>(tile_in + ((uint64_t)bitrev_c((uint32_t)e, LOGR) << rshift), ld_lane);
     }
   }
 
@@ -288,10 +376,9 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
         const int i = ((m >> (s - s0)) << (s - s0 + 1)) | (m & (d - 1));
         be0[b] = gi * (1 << q) + i;
         be1[b] = be0[b] + d;
-        const uint32_t gamma = (uint32_t)(t * G + gi);
-        const uint32_t bpos = (gamma & ((1u << s0) - 1u)) | ((gamma >> s0) << (s0 + q));
-        const uint32_t pos = bpos + ((uint32_t)i << s0);
-        bj[b] = pos & ((1u << s) - 1u);
+        // (lane part + compile-time part of the position, as pos_lane below)
+        bj[b] = (phase_bpos((uint32_t)(t * G), s0, q) & ((1u << s) - 1u)) +
+                (phase_pos_c(s0, q, gi * (1 << q) + i) & ((1u << s) - 1u));
         // phase 1: j is a compile-time function of i (s == 0 or j == 0: w = 1)
         btriv[b] = s0 == 0 && (s == 0 || (i & ((1 << s) - 1)) == 0);
       }
@@ -331,34 +418,37 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
       }
     }
   };
-  auto positions = [&](auto S0_, auto Q_, uint32_t (&pos)[EPT]) {
+  // the lane part of the phase's positions: element e is at pos_lane + pos_c(e)
+  auto pos_lane = [&](auto S0_, auto Q_) -> uint32_t {
     constexpr int s0 = decltype(S0_)::value;
     constexpr int q = decltype(Q_)::value;
-    constexpr int G = EPT >> q;
-#pragma unroll
-    for (int gi = 0; gi < G; ++gi) {
-      const uint32_t gamma = (uint32_t)(t * G + gi);
-      const uint32_t bpos = (gamma & ((1u << s0) - 1u)) | ((gamma >> s0) << (s0 + q));
-#pragma unroll
-      for (int i = 0; i < (1 << q); ++i) pos[gi * (1 << q) + i] = bpos + ((uint32_t)i << s0);
-    }
+    return phase_bpos((uint32_t)(t * (EPT >> q)), s0, q);
   };
 
   using I0 = std::integral_constant<int, 0>;
   constexpr int Q1 = LOGR < LQ ? LOGR : LQ;
   run_phase(I0{}, std::integral_constant<int, Q1>{});
-  uint32_t pos[EPT];
-  positions(I0{}, std::integral_constant<int, Q1>{}, pos);
+  uint32_t pos0 = pos_lane(I0{}, std::integral_constant<int, Q1>{});
+  // the last register phase: its positions are the rows of the epilogue
+  constexpr int kS0F = LOGR > 2 * LQ ? 2 * LQ : (LOGR > LQ ? LQ : 0);
+  constexpr int kQF = LOGR - kS0F;
+  auto pos_c = [](int e) -> uint32_t { return phase_pos_c(kS0F, kQF, e); };
 
   // ---- remaining phases through LDS -------------------------------------
-  auto exchange_and_run = [&](auto S0_, auto Q_) {
+  // One address VGPR per direction: element e is pos_c(e) * kCols * 16 bytes
+  // from the lane's slot, an immediate of the ds instruction.
+  auto exchange_and_run = [&](auto PS0_, auto PQ_, auto S0_, auto Q_) {
+    constexpr int ps0 = decltype(PS0_)::value, pq = decltype(PQ_)::value;
+    constexpr int s0 = decltype(S0_)::value, q = decltype(Q_)::value;
     __syncthreads();  // previous phase's reads of lds are done
+    fe* wr = &lds[pos0 * kCols + c];
 #pragma unroll
-    for (int e = 0; e < EPT; ++e) fe_store(&lds[pos[e] * kCols + c], x[e]);
+    for (int e = 0; e < EPT; ++e) fe_store(wr + phase_pos_c(ps0, pq, e) * kCols, x[e]);
     __syncthreads();
-    positions(S0_, Q_, pos);
+    pos0 = pos_lane(S0_, Q_);
+    const fe* rd = &lds[pos0 * kCols + c];
 #pragma unroll
-    for (int e = 0; e < EPT; ++e) x[e] = fe_load(&lds[pos[e] * kCols + c]);
+    for (int e = 0; e < EPT; ++e) x[e] = fe_load(rd + phase_pos_c(s0, q, e) * kCols);
     run_phase(S0_, Q_);
   };
   // Two-table twiddle: TB[k][jh] has one jh for the tile's 8 columns (loga >=
@@ -372,7 +462,15 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
   constexpr int NTt = kCols * R / EPT;
   constexpr int kTbPerThread = TW == 0 ? R / NTt : 1;
   fe tbv[kTbPerThread][4];
-  const uint64_t jl = jrest & ((1ull << g.loga) - 1);
+  // TA[k][jl], jl = jrest mod 2^loga = (jcol0 mod 2^loga) + cB (loga >= 3): row
+  // pos_c(e) and the tile's first jl go to the base, the lane keeps
+  // ((pos0 << loga) + cB) * 16
+  const fe* ta_tile = ta + (jcol0 & ((1ull << g.loga) - 1));
+  auto ta_lane_of = [&](uint32_t p0) -> Off { return (((Off)p0 << g.loga) + (Off)cB) << 4; };
+  auto ta_at = [&](int e, Off lane) -> fe {
+    return fe_load_at<Off>(ta_tile + ((uint64_t)pos_c(e) << g.loga), lane);
+  };
+  Off ta_lane = 0;
   fe ta_c0, ta_c1;
   // MLH_TB_COALESCED: the 4R dwordx4 pieces of the tile's TB column are dealt
   // to the threads in order (piece i = part i mod 4 of row i / 4), so 4
@@ -386,35 +484,42 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
 #endif
   auto load_tb = [&]() {
     if constexpr (TW == 0 && MLH_DIAG_TW == 0) {
-      const uint64_t jh = jrest >> g.loga;  // the same for the whole tile (loga >= 3)
+      const uint64_t jh = jcol0 >> g.loga;  // the same for the whole tile (loga >= 3)
       const uint32_t ltcols = g.lstride - g.loga;
+      const fe* tb_tile = tb + (jh << 2);
+#if MLH_TB_COALESCED
+      static_assert(NTt % 4 == 0, "a round of pieces is whole rows");
+      const Off tb_lane = ((((Off)(tid >> 2) << ltcols) << 2) + (Off)(tid & 3)) << 4;
+#else
+      const Off tb_lane = (((Off)tid << ltcols) << 2) << 4;
+#endif
 #pragma unroll
       for (int e = 0; e < kTbPerThread; ++e) {
-#if MLH_TB_COALESCED
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const uint32_t i = (uint32_t)((e * 4 + k) * NTt + tid);
-          tbv[e][k] = fe_load(tb + ((((uint64_t)(i >> 2) << ltcols) + jh) << 2) + (i & 3));
-        }
+#if MLH_TB_COALESCED
+          // piece i = (e 4 + k) NTt + tid: row i / 4 = (e 4 + k) NTt / 4 + tid / 4
+          tbv[e][k] = fe_load_at<Off>(tb_tile + (((uint64_t)((e * 4 + k) * (NTt / 4)) << ltcols) << 2), tb_lane);
 #else
-        const fe* q = tb + ((((uint64_t)(e * NTt + tid) << ltcols) + jh) << 2);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) tbv[e][k] = fe_load(q + k);
+          tbv[e][k] = fe_load_at<Off>(tb_tile + (((uint64_t)(e * NTt) << ltcols) << 2) + k, tb_lane);
 #endif
+        }
       }
     }
   };
   // the first pair's inter-pass twiddles (the asm products below keep later
-  // loads from being hoisted, so each pair's are issued one pair ahead)
-  auto load_ta0 = [&](const uint32_t (&pf)[EPT]) {
+  // loads from being hoisted, so each pair's are issued one pair ahead);
+  // p0: the lane part of the last phase's positions
+  auto load_ta0 = [&](uint32_t p0) {
     if constexpr (TW == 5) {
-      (void)pf;
+      (void)p0;
     } else if constexpr (!LAST && MLH_DIAG_TW == 2) {
-      ta_c0 = fe{{(uint32_t)jl | 1u, 7u, 9u, 3u}};
-      ta_c1 = fe{{(uint32_t)pf[1] | 1u, 5u, 9u, 3u}};
+      ta_c0 = fe{{(uint32_t)jrest | 1u, 7u, 9u, 3u}};
+      ta_c1 = fe{{(uint32_t)p0 | 1u, 5u, 9u, 3u}};
     } else if constexpr (!LAST) {
-      ta_c0 = fe_load(ta + ((uint64_t)pf[0] << g.loga) + jl);
-      ta_c1 = fe_load(ta + ((uint64_t)pf[1] << g.loga) + jl);
+      ta_lane = ta_lane_of(p0);
+      ta_c0 = ta_at(0, ta_lane);
+      ta_c1 = ta_at(1, ta_lane);
     }
   };
 #ifndef MLH_P0_EARLY_TB
@@ -424,46 +529,61 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
   constexpr bool kEarly = MLH_P0_EARLY_TB && TW == 0 && LOGR > 2 * LQ;
   if constexpr (LOGR > LQ) {
     constexpr int Q2 = (LOGR - LQ) < LQ ? (LOGR - LQ) : LQ;
+    using IQ1 = std::integral_constant<int, Q1>;
+    using ILQ = std::integral_constant<int, LQ>;
+    using IQ2 = std::integral_constant<int, Q2>;
     if constexpr (kDirect) {
       // written in the phase-1 map, read in the 8-columns-per-row map; the
       // column slot is XORed with the row's top 3 bits, so the 8 lanes of a
       // write group (consecutive l: distinct top bits of t) and of a read
-      // group (8 columns of one row) each hit 8 distinct 16-B slots
-      auto slot = [&](uint32_t row, int col) -> uint32_t {
-        return row * kCols + ((uint32_t)col ^ ((row >> (LOGR - 3)) & (kCols - 1)));
+      // group (8 columns of one row) each hit 8 distinct 16-B slots.
+      // row = pos0 + pos_c on disjoint bits, so the XOR term is (lane part) ^
+      // (constant part sc).  The writes have sc = 0 (phase 1's pos_c < 8): one
+      // address VGPR plus immediates.  The reads are additive only among the
+      // elements with the same sc (R = 2^9: all; 2^8: two values; 2^7: four;
+      // 2^6: eight, i.e. not at all): one address VGPR per distinct sc.
+      auto slot0 = [&](uint32_t p0, int col) -> uint32_t {
+        return p0 * kCols + ((uint32_t)col ^ ((p0 >> (LOGR - 3)) & (kCols - 1)));
       };
       __syncthreads();  // (the twiddle copy's writes, before the phase-2 reads of lds_tw)
+      static_assert((phase_pos_c(0, Q1, EPT - 1) >> (LOGR - 3)) == 0, "phase 1: constant rows below the swizzle bits");
+      fe* wr = &lds[slot0(pos0, c)];
 #pragma unroll
-      for (int e = 0; e < EPT; ++e) fe_store(&lds[slot(pos[e], c)], x[e]);
+      for (int e = 0; e < EPT; ++e) fe_store(wr + phase_pos_c(0, Q1, e) * kCols, x[e]);
       __syncthreads();
       c = cB;
       t = tid / kCols;
-      positions(std::integral_constant<int, LQ>{}, std::integral_constant<int, Q2>{}, pos);
+      pos0 = pos_lane(ILQ{}, IQ2{});
+      const uint32_t rd0 = slot0(pos0, c);
 #pragma unroll
-      for (int e = 0; e < EPT; ++e) x[e] = fe_load(&lds[slot(pos[e], c)]);
-      run_phase(std::integral_constant<int, LQ>{}, std::integral_constant<int, Q2>{});
+      for (int e = 0; e < EPT; ++e) {
+        const uint32_t pc = phase_pos_c(LQ, Q2, e);
+        const uint32_t sc = (pc >> (LOGR - 3)) & (kCols - 1);
+        x[e] = fe_load(&lds[(rd0 ^ sc) + pc * kCols]);
+      }
+      run_phase(ILQ{}, IQ2{});
     } else {
-      exchange_and_run(std::integral_constant<int, LQ>{}, std::integral_constant<int, Q2>{});
+      exchange_and_run(I0{}, IQ1{}, ILQ{}, IQ2{});
     }
     if constexpr (LOGR > 2 * LQ) {
       constexpr int Q3 = LOGR - 2 * LQ;
       static_assert(Q3 <= LQ, "LOGR <= 3 * LQ");
+      using I2LQ = std::integral_constant<int, 2 * LQ>;
+      using IQ3 = std::integral_constant<int, Q3>;
       if constexpr (kEarly) {
-        uint32_t pf[EPT];
-        positions(std::integral_constant<int, 2 * LQ>{}, std::integral_constant<int, Q3>{}, pf);
         load_tb();
-        if (MLH_P0_EARLY_TB == 1) load_ta0(pf);  // 2: TB only
+        if (MLH_P0_EARLY_TB == 1) load_ta0(pos_lane(I2LQ{}, IQ3{}));  // 2: TB only
       }
-      exchange_and_run(std::integral_constant<int, 2 * LQ>{}, std::integral_constant<int, Q3>{});
+      exchange_and_run(ILQ{}, IQ2{}, I2LQ{}, IQ3{});
     }
   }
 
   // ---- epilogue: inter-pass twiddle, store --------------------------------
   if constexpr (!kEarly) {
-    load_ta0(pos);
+    load_ta0(pos0);
     load_tb();
   } else if (MLH_P0_EARLY_TB == 2) {
-    load_ta0(pos);
+    load_ta0(pos0);
   }
   if constexpr (TW == 0) {
     static_assert(4 * R <= R * kCols, "the expanded TB column fits the exchange tile");
@@ -476,22 +596,27 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
         lds[MLH_TB_COALESCED ? (e * 4 + k) * NT + tid : 4 * (e * NT + tid) + k] = tbv[e][k];
     __syncthreads();
   }
-  uint64_t kbase = 0;
-  uint32_t kshift = 0;
-  if (LAST) {
-    kbase = k1 + (reverse_mid_digits(g, mid) << g.logr[0]);
-    kshift = g.log_n - LOGR;
-  }
+  // the lane's byte offset into the output tile (rows rshift apart, the 8
+  // columns cshift apart); row pos_c(e) goes to the base
+  Off st_lane = (((Off)pos0 << rshift) + ((Off)cB << cshift)) << 4;
+  auto store_row = [&](int e) {
+    fe_store_at<Off>(tile_out + ((uint64_t)pos_c(e) << rshift), st_lane, x[e]);
+  };
   if constexpr (TW == 5) {
     constexpr int Q3 = LOGR - 2 * LQ, NI = 1 << Q3, G = EPT / NI;
     static_assert(LOGR > 2 * LQ && G % 2 == 0, "progression twiddle: groups in pairs");
     // (loaded here: issued before the last register phase instead -- P alone,
     // or P and C with 6 spilled registers -- measured no faster / 8 % slower)
-    fe tv[G];  // P[k0][j] of each group (k0 = pos[g NI]: the group's first row)
+    // P[k0][j] of each group (k0 = pos0 + pos_c(g NI): the group's first row);
+    // P has the tile's row stride, so the lane's offset is the store's
+    fe tv[G];
 #pragma unroll
-    for (int gq = 0; gq < G; ++gq) tv[gq] = fe_load(ta + ((uint64_t)pos[gq * NI] << g.lstride) + jrest);
-    const fe* cp = tb + 4 * jrest;
-    const fe c0 = fe_load(cp), c1 = fe_load(cp + 1), c2 = fe_load(cp + 2), c3 = fe_load(cp + 3);
+    for (int gq = 0; gq < G; ++gq)
+      tv[gq] = fe_load_at<Off>(ta + jcol0 + ((uint64_t)pos_c(gq * NI) << g.lstride), st_lane);
+    const fe* cp = tb + 4 * jcol0;
+    const Off c_lane = (Off)cB << 6;
+    const fe c0 = fe_load_at<Off>(cp, c_lane), c1 = fe_load_at<Off>(cp + 1, c_lane),
+             c2 = fe_load_at<Off>(cp + 2, c_lane), c3 = fe_load_at<Off>(cp + 3, c_lane);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       uint64_t rare;
@@ -499,8 +624,9 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
       for (int gq = 0; gq < G; gq += 2) {
         const int e0 = gq * NI + i, e1 = (gq + 1) * NI + i;
         bfly_ff_v(x[e0], tv[gq], x[e1], tv[gq + 1], rare);
-        fe_store(dst + ((uint64_t)pos[e0] << rshift), x[e0]);
-        fe_store(dst + ((uint64_t)pos[e1] << rshift), x[e1]);
+        pin_lane_offset(st_lane);
+        store_row(e0);
+        store_row(e1);
       }
       if (i + 1 < NI) {
 #pragma unroll
@@ -512,39 +638,73 @@ ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
     // consecutive jl, so a wave's lanes read 8 runs of 128 B per table.  The
     // products run two elements per generated asm statement (relaxed result;
     // bfly_asm.hpp), and the next pass takes relaxed input.
+    const fe* tb_rows = lds + 4 * pos0;  // the staged TB column: entry of row pos0 + pos_c(e)
 #pragma unroll
     for (int e = 0; e < EPT; e += 2) {
       uint64_t rare;
       const fe a0 = ta_c0, a1 = ta_c1;
       if (e + 2 < EPT && MLH_DIAG_TW < 2) {  // the next pair's, in flight during this pair's products
-        ta_c0 = fe_load(ta + ((uint64_t)pos[e + 2] << g.loga) + jl);
-        ta_c1 = fe_load(ta + ((uint64_t)pos[e + 3] << g.loga) + jl);
+        pin_lane_offset(ta_lane);
+        ta_c0 = ta_at(e + 2, ta_lane);
+        ta_c1 = ta_at(e + 3, ta_lane);
       }
       bfly_ff_v(x[e], a0, x[e + 1], a1, rare);
       if constexpr (TW == 0 && MLH_DIAG_TW == 0) {
-        const fe* b0 = lds + 4 * pos[e];
-        const fe* b1 = lds + 4 * pos[e + 1];
+        const fe* b0 = tb_rows + 4 * pos_c(e);
+        const fe* b1 = tb_rows + 4 * pos_c(e + 1);
         bfly_pp_v(x[e], b0[0], b0[1], b0[2], b0[3], x[e + 1], b1[0], b1[1], b1[2], b1[3], rare);
       }
-      fe_store(dst + ((uint64_t)pos[e] << rshift), x[e]);
-      fe_store(dst + ((uint64_t)pos[e + 1] << rshift), x[e + 1]);
+      pin_lane_offset(st_lane);
+      store_row(e);
+      store_row(e + 1);
     }
+    (void)tb_rows;
   } else {
     // canonical output, four elements per asm statement
     static_assert(EPT % 4 == 0, "canonicalisation in fours");
 #pragma unroll
     for (int e = 0; e < EPT; e += 4) bfly_cccc_v(x[e], x[e + 1], x[e + 2], x[e + 3]);
+    // natural index K = k1 + R_1 rev(mid) + (pos << kshift), k1 = k1u + cB:
+    // all but (pos0 << kshift) + cB is wave-uniform
+    const uint32_t kshift = g.log_n - LOGR;
+    const uint64_t kbase_u = k1u + (reverse_mid_digits(g, mid) << g.logr[0]);
+    if constexpr (SH) {
 #pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      uint64_t K = kbase + ((uint64_t)pos[e] << kshift);
-      if constexpr (SH) {  // drop the rank bits [logr0 - p, logr0) of K
+      for (int e = 0; e < EPT; ++e) {
+        uint64_t K = kbase_u + cB + ((uint64_t)(pos0 + pos_c(e)) << kshift);
+        // drop the rank bits [logr0 - p, logr0) of K
         const uint32_t lo = g.logr[0] - g.sh_p;
         K = ((K >> g.logr[0]) << lo) | (K & ((1ull << lo) - 1));
+        fe_store(out + K, x[e]);
       }
-      fe_store(out + K, x[e]);
+    } else {
+      const Off k_lane = (((Off)pos0 << kshift) + (Off)cB) << 4;
+#pragma unroll
+      for (int e = 0; e < EPT; ++e)
+        fe_store_at<Off>(out + kbase_u + ((uint64_t)pos_c(e) << kshift), k_lane, x[e]);
     }
   }
+  (void)store_row;
+  (void)st_lane;
+  (void)ld_lane;
+  (void)jrest;
   (void)TPC;
+}
+
+template <int LOGR, int TW, int ZT, int EPT = kEPT>
+__global__ void __launch_bounds__(kCols * (1 << LOGR) / EPT,
+                                  (TW == 2 || TW == 4) ? 1 : pass_waves_per_simd(LOGR, EPT))
+ntt_pass_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
+                const fe* __restrict__ ta, const fe* __restrict__ tb, PassGeom g) {
+  ntt_pass_body<LOGR, TW, ZT, EPT, false>(in, out, tw, ta, tb, g);
+}
+
+template <int LOGR, int TW, int ZT, int EPT = kEPT>
+__global__ void __launch_bounds__(kCols * (1 << LOGR) / EPT,
+                                  (TW == 2 || TW == 4) ? 1 : pass_waves_per_simd(LOGR, EPT))
+ntt_pass_wide_kernel(const fe* in, fe* out, const fe* __restrict__ tw,
+                     const fe* __restrict__ ta, const fe* __restrict__ tb, PassGeom g) {
+  ntt_pass_body<LOGR, TW, ZT, EPT, true>(in, out, tw, ta, tb, g);
 }
 
 // Single-workgroup NTT for N <= 2^10: LDS-resident radix-2 DIT.
@@ -792,12 +952,18 @@ hipError_t launch_ntt_network(const fe* in, fe* out, fe* scratch, const fe* tlo,
 template <int LOGR, int EPT>
 static hipError_t launch_pass_ept(bool last, int zero_top, const fe* in, fe* out, const fe* tw,
                                   const fe* ta, const fe* tb, const PassGeom& g, uint64_t tiles,
-                                  hipStream_t st, bool geo = false) {
+                                  hipStream_t st, bool geo, bool wide) {
   constexpr int threads = kCols * (1 << LOGR) / EPT;
   const dim3 grid((unsigned)tiles), blk(threads);
-#define MLH_PASS(TWV, ZTV)                                                                  \
-  hipLaunchKernelGGL((ntt_pass_kernel<LOGR, TWV, ZTV, EPT>), grid, blk, MLH_LDS_PAD, st, in, out, \
-                     tw, ta, tb, g)
+#define MLH_PASS(TWV, ZTV)                                                                        \
+  do {                                                                                            \
+    if (wide)                                                                                     \
+      hipLaunchKernelGGL((ntt_pass_wide_kernel<LOGR, TWV, ZTV, EPT>), grid, blk, MLH_LDS_PAD, st, \
+                         in, out, tw, ta, tb, g);                                                 \
+    else                                                                                          \
+      hipLaunchKernelGGL((ntt_pass_kernel<LOGR, TWV, ZTV, EPT>), grid, blk, MLH_LDS_PAD,          \
+                         st, in, out, tw, ta, tb, g);                                             \
+  } while (0)
   if (last) {
     if (zero_top) return hipErrorInvalidValue;  // pass 0 is never the last pass here
     MLH_PASS(2, 0);
@@ -831,8 +997,19 @@ static hipError_t launch_pass_ept(bool last, int zero_top, const fe* in, fe* out
 template <int LOGR>
 static hipError_t launch_pass(bool last, int zero_top, const fe* in, fe* out, const fe* tw,
                               const fe* ta, const fe* tb, const PassGeom& g, uint64_t tiles,
-                              hipStream_t st, bool geo = false) {
-  return launch_pass_ept<LOGR, kEPT>(last, zero_top, in, out, tw, ta, tb, g, tiles, st, geo);
+                              hipStream_t st, bool geo, bool wide) {
+  return launch_pass_ept<LOGR, kEPT>(last, zero_top, in, out, tw, ta, tb, g, tiles, st, geo, wide);
+}
+
+// Whether a pass needs 64-bit per-lane offsets: its largest byte offset from a
+// wave-uniform base reaches 2^32.  A pass before the last spans its tile, R
+// rows 2^lstride elements apart (its tables are smaller: TA at most
+// 2^kFullTwLog entries, TB R * W / 2^loga expanded ones, the progression 64 W);
+// the last pass's natural-order stores span the vector.  So 2^28 is the
+// largest transform whose first and last passes take the narrow form.
+static bool pass_wide(const NttTables& tb, uint32_t log_n, uint32_t lr, uint32_t lstride, bool last) {
+  if (tb.wide_offsets) return true;
+  return (last ? log_n : lr + lstride) + 4 > 32;
 }
 
 void ntt_plan_radices(uint32_t log_n, uint32_t* nradix, uint32_t* logr, const uint32_t* forced,
@@ -911,13 +1088,14 @@ hipError_t launch_ntt_passes(const fe* in, fe* out, fe* scratch, const NttTables
     const bool geo = tb.gp[p] != nullptr;  // TW 5: the progression tables instead of TA, TB
     const fe* ta = geo ? tb.gp[p] : tb.ta[p];
     const fe* tbb = geo ? tb.gc[p] : tb.tb[p];
+    const bool wide = pass_wide(tb, log_n, lr, g.lstride, last);
     switch (lr) {
-      case 4: e = launch_pass<4>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo); break;
-      case 5: e = launch_pass<5>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo); break;
-      case 6: e = launch_pass<6>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo); break;
-      case 7: e = launch_pass<7>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo); break;
-      case 8: e = launch_pass<8>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo); break;
-      case 9: e = launch_pass<9>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo); break;
+      case 4: e = launch_pass<4>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo, wide); break;
+      case 5: e = launch_pass<5>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo, wide); break;
+      case 6: e = launch_pass<6>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo, wide); break;
+      case 7: e = launch_pass<7>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo, wide); break;
+      case 8: e = launch_pass<8>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo, wide); break;
+      case 9: e = launch_pass<9>(last, zt, src, dst, tb.tw[p], ta, tbb, g, tiles, st, geo, wide); break;
       default: return hipErrorInvalidValue;
     }
     if (e != hipSuccess) return e;
@@ -973,14 +1151,15 @@ hipError_t launch_ntt_passes_pre(const fe* in, fe* out, const NttTables& tb, uin
     g.lin_v = g.lout_v = log_n;
     const uint64_t tiles = N >> (kLogCols + lr);
     const fe* src = p == 0 ? in : out;  // pass 0: in -> out; then in place on out
+    const bool wide = pass_wide(tb, log_n, lr, g.lstride, false);
     hipError_t e;
     switch (lr) {
-      case 4: e = launch_pass<4>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st); break;
-      case 5: e = launch_pass<5>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st); break;
-      case 6: e = launch_pass<6>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st); break;
-      case 7: e = launch_pass<7>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st); break;
-      case 8: e = launch_pass<8>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st); break;
-      case 9: e = launch_pass<9>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st); break;
+      case 4: e = launch_pass<4>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st, false, wide); break;
+      case 5: e = launch_pass<5>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st, false, wide); break;
+      case 6: e = launch_pass<6>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st, false, wide); break;
+      case 7: e = launch_pass<7>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st, false, wide); break;
+      case 8: e = launch_pass<8>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st, false, wide); break;
+      case 9: e = launch_pass<9>(false, 0, src, out, tb.tw[p], tb.ta[p], tb.tb[p], g, tiles, st, false, wide); break;
       default: return hipErrorInvalidValue;
     }
     if (e != hipSuccess) return e;

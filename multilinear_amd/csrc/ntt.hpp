@@ -50,6 +50,7 @@ struct NttTables {
   fe scale;                              // n^-1 (inverse) or 1
   bool inverse = false;
   bool debug_sync = false;               // sync after every pass (MLH_DEBUG_SYNC at context creation)
+  bool wide_offsets = false;             // every pass with 64-bit lane offsets (MLH_NTT_WIDE_OFFSETS at context creation)
 };
 
 // Radix plan of a 2^log_n transform: the default, or `forced` (nforced

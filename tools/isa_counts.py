@@ -4,7 +4,12 @@ butterflies' out-of-line rare-correction blocks, counted apart as valu_cold /
 s_nop_cold).  Compiles ntt.hip for gfx950 to assembly and writes
 profiles/isa_counts.json:
   {"ntt_pass<8,0,0>": {"valu": .., "mad_u64": .., "salu": .., "lds": .., "vmem": ..,
-                       "vgpr": .., "ept": 8}, ...}
+                       "vgpr": .., "ept": 8, "valu_outside_asm": .., "v_mov": ..,
+                       "sgpr": .., "scratch_bytes": ..}, ...}
+valu_outside_asm: hot-path VALU the compiler adds around the generated asm
+statements (addresses, copies); v_mov: hot-path v_mov_b32, inside or outside
+(v_mov_outside_asm: those outside).
+The 64-bit-offset kernels (ntt_pass_wide_kernel) are listed as "ntt_pass<..>/wide".
 Run on the build host (no GPU):  python tools/isa_counts.py"""
 import collections
 import json
@@ -60,15 +65,21 @@ def main():
         text = open(asm).read()
     out = {}
     # kernel bodies: "<mangled>:  ; @<mangled>" ... "s_endpgm"
-    for m in re.finditer(r"\n(_ZN3mlh15ntt_pass_kernelILi(\d+)ELi(\d)ELi(\d)ELi(\d+)\w*):\s*;\s*@",
+    for m in re.finditer(r"\n(_ZN3mlh(?:15ntt_pass_kernel|20ntt_pass_(wide)_kernel)ILi(\d+)ELi(\d)ELi(\d)ELi(\d+)\w*):\s*;\s*@",
                          text):
-        name, logr, tw, zt, ept = m.group(1), m.group(2), m.group(3), m.group(4), m.group(5)
+        name, logr, tw, zt, ept = m.group(1), m.group(3), m.group(4), m.group(5), m.group(6)
+        wide = m.group(2) == "wide"
         end = text.index("s_endpgm", m.end())
         body = text[m.end():end]
         lines = body.split("\n")
         cold = cold_lines(lines)
         c = collections.Counter()
+        inasm = False
         for ln, line in enumerate(lines):
+            if "ASMSTART" in line:
+                inasm = True
+            elif "ASMEND" in line:
+                inasm = False
             t = re.match(r"\s+([vsdgb][a-z_0-9]+)", line)
             if not t:
                 continue
@@ -81,6 +92,12 @@ def main():
                 continue
             if op.startswith("v_"):
                 c["valu"] += 1
+                if not inasm:
+                    c["valu_outside_asm"] += 1
+                if op.startswith("v_mov_b32"):
+                    c["v_mov"] += 1
+                    if not inasm:
+                        c["v_mov_outside_asm"] += 1
                 if op == "v_mad_u64_u32":
                     c["mad_u64"] += 1
             elif op.startswith("s_") and not op.startswith(("s_nop", "s_waitcnt", "s_barrier",
@@ -96,7 +113,15 @@ def main():
         lab = "ntt_pass<%s,%s,%s>" % (logr, tw, zt)
         if int(ept) != 8:
             lab += "/ept%s" % ept
+        if wide:
+            lab += "/wide"
+        c.setdefault("valu_outside_asm", 0)
+        c.setdefault("v_mov", 0)
+        c.setdefault("v_mov_outside_asm", 0)
         out[lab] = dict(c, ept=int(ept), vgpr=int(meta.group(2)) if meta else None)
+        for key, field in (("sgpr", "sgpr_count"), ("scratch_bytes", "private_segment_fixed_size")):
+            f = re.search(r"\.%s:\s+(\d+)" % field, meta.group(1)) if meta else None
+            out[lab][key] = int(f.group(1)) if f else None
     dst = os.path.join(ROOT, "profiles", "isa_counts.json")
     json.dump(out, open(dst, "w"), indent=1, sort_keys=True)
     print("wrote", dst, "kernels:", len(out))
