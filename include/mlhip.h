@@ -872,6 +872,63 @@ mlh_status mlh_trace_fill_shaped(mlh_ctx* ctx, const mlh_fill_program* prog, voi
 mlh_status mlh_trace_column_sum(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
                                 uint32_t width, uint32_t column_mask, uint8_t out[16]);
 
+/* ---- a lookup's multiplicities on the device -------------------------------- *
+ * The multiplicity column m of a log-derivative lookup (v = -m / (gamma - t))
+ * is a pre-random column: it must stand in the matrix before
+ * mlh_trace_commit_range of the first column range.  This call counts it in
+ * place, with no host copy of a column.
+ * Let key(j) = matrix[j][table_column] as 16 bytes; row j is the owner of its
+ * key when no lower row has the same key.  After the call
+ *   matrix[j][count_column] = the number of pairs (i, c), c in
+ *     value_column_mask, with matrix[i][c] == key(j), as a canonical element,
+ *     when j is an owner, and zero otherwise (a table padded by repeating an
+ *     entry: the lowest row takes the whole count);
+ *   *n_missing = the number of pairs (i, c) whose value equals no table entry;
+ *   *first_missing_row = the lowest such i, UINT64_MAX when there is none;
+ * and no other column is written.  A missing value is no error: MLH_OK, and
+ * the counts of the values that were found are right.  Equality is equality of
+ * the 16 bytes (canonical inputs are the caller's contract).  The result is a
+ * pure function of the matrix: it does not depend on the launch shape, on where
+ * the hash puts a key or on the order of the atomics.
+ * width 1..32, log_height 0..28 (row indices are 32-bit with one value
+ * reserved).  MLH_ERR_INVALID for an empty mask, a mask bit, table_column or
+ * count_column at or above width, table_column == count_column, either of them
+ * in the mask, and NULL pointers; the matrix is then untouched.
+ * A hash join with open addressing over row indices in a pooled scratch array
+ * of 2^log_slots 32-bit slots, log_slots = log_height + 2 (16 bytes per row):
+ * one launch inserts the table rows (and zeroes the count column), a second
+ * counts one (row, value column) pair per thread with a 64-bit atomic add into
+ * the owner's count element, the lanes of a wave that found the same owner
+ * combined and kept in a per-wave cache so that a few hot entries cost one add
+ * per wave.  Every probe loop is bounded by the number of slots.  Both
+ * launches: 256 threads, min(ceil(work / 256), 1024) blocks looping with the
+ * grid's stride, work = 2^log_height rows, times the number of value columns
+ * for the count.  Synchronises once to return the two counters. */
+mlh_status mlh_trace_lookup_counts(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                   uint32_t width, uint32_t value_column_mask,
+                                   uint32_t table_column, uint32_t count_column,
+                                   uint64_t* n_missing, uint64_t* first_missing_row);
+/* Its launch shape: threads per block (256), blocks of the count launch
+ * (min(ceil(2^log_height * n_value_columns / 256), 1024)) and log_slots
+ * (log_height + 2).  n_value_columns 1..30, log_height 0..28. */
+mlh_status mlh_trace_lookup_counts_launch_info(uint32_t log_height, uint32_t n_value_columns,
+                                               uint32_t* threads, uint32_t* blocks,
+                                               uint32_t* log_slots);
+/* The same bytes under another shape, for tests of the probe paths at small
+ * heights and for measurements.  log_slots log_height..31; hash_bits 0..
+ * log_slots keeps that many low bits of the slot hash (0: every key starts at
+ * slot 0 and the table is one probe chain); max_blocks caps both grids (0: the
+ * rule above); flags bit 0 turns the wave-level combining off (one atomic per
+ * lane), every other bit is MLH_ERR_INVALID, as are log_slots and hash_bits
+ * outside those ranges.  With log_slots == log_height and distinct keys the
+ * slot array is full and a missing value ends at the probe bound. */
+mlh_status mlh_trace_lookup_counts_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                          uint32_t width, uint32_t value_column_mask,
+                                          uint32_t table_column, uint32_t count_column,
+                                          uint64_t* n_missing, uint64_t* first_missing_row,
+                                          uint32_t log_slots, uint32_t hash_bits,
+                                          uint32_t max_blocks, uint32_t flags);
+
 /* ---- multilinear PCS (src/fri/multilinear_pcs.rs) ------------------------ */
 typedef struct mlh_pcs_proof {
   mlh_fri_proof fri;

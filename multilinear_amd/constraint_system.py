@@ -18,7 +18,9 @@ columns and hands out the trace randoms, the caller fills the other columns
 ``inv``, run in place by mlh_trace_fill; or ``field_inv`` and the other field
 ops below on column vectors), and ``prove`` / ``PhasedSystemProof.verify`` are
 mlh_system_prove_phased / _verify_phased, the column sum by default from
-mlh_trace_column_sum.
+mlh_trace_column_sum.  A lookup's multiplicity column, which is pre-random, is
+counted in place before ``phased_prover`` by ``Trace.lookup_multiplicities``
+(mlh_trace_lookup_counts).
 """
 import ctypes
 import struct
@@ -368,6 +370,56 @@ class Trace:
         check(lib().mlh_trace_fill(ctx, prog.h, ptr(self._matrix), self._height.bit_length() - 1,
                                    self._width, _elems(randoms)), ctx)
         return prog
+
+    def lookup_counts(self, value_columns, table_column, count_column, device=0):
+        """A lookup's multiplicities, in place (mlh_trace_lookup_counts): column
+        ``count_column`` of the lowest row holding each entry of ``table_column``
+        receives how often that entry occurs in ``value_columns``, the other
+        rows zero.  Returns (n_missing, first_missing_row): the (row, value
+        column) pairs whose value is no table entry and the lowest such row,
+        None when nothing is missing."""
+        mask = _lookup_mask(self._width, value_columns, table_column, count_column)
+        ctx = context(device)
+        n, first = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().mlh_trace_lookup_counts(ctx, ptr(self._matrix), self._height.bit_length() - 1,
+                                            self._width, mask, table_column, count_column,
+                                            ctypes.byref(n), ctypes.byref(first)), ctx)
+        return n.value, (None if first.value == 2 ** 64 - 1 else first.value)
+
+    def lookup_multiplicities(self, value_columns, table_column, count_column, device=0):
+        """lookup_counts for a lookup that must hold: ValueError naming the
+        first row with a value that is no table entry."""
+        n, first = self.lookup_counts(value_columns, table_column, count_column, device)
+        if n:
+            raise ValueError("%d looked-up value%s not in table column %d, the first in row %d"
+                             % (n, "" if n == 1 else "s", table_column, first))
+
+
+def _lookup_mask(width, value_columns, table_column, count_column):
+    """The value-column mask of a lookup, its columns checked (ValueError)."""
+    mask = 0
+    for j in value_columns:
+        if not 0 <= j < width:
+            raise ValueError("value column %r outside the trace" % (j,))
+        mask |= 1 << j
+    if not mask:
+        raise ValueError("a lookup needs a value column")
+    for name, j in (("table", table_column), ("count", count_column)):
+        if not 0 <= j < width:
+            raise ValueError("%s column %r outside the trace" % (name, j))
+        if (mask >> j) & 1:
+            raise ValueError("the %s column %d is a value column" % (name, j))
+    if table_column == count_column:
+        raise ValueError("the table column and the count column are both %d" % table_column)
+    return mask
+
+
+def lookup_counts_launch_info(log_height, n_value_columns):
+    """(threads per block, blocks of the count launch, log2 of the slots)."""
+    t, b, s = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    check(lib().mlh_trace_lookup_counts_launch_info(log_height, n_value_columns, ctypes.byref(t),
+                                                    ctypes.byref(b), ctypes.byref(s)))
+    return t.value, b.value, s.value
 
 
 def trace_column_sum(dev_matrix, width, columns, device=0):

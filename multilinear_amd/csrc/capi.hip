@@ -48,6 +48,7 @@
 #include "tables.hpp"
 #include "trace_commit.hpp"
 #include "trace_fill.hpp"
+#include "trace_lookup.hpp"
 #include "transcript_dev.hpp"
 
 using namespace mlh;
@@ -1242,6 +1243,73 @@ mlh_status mlh_trace_column_sum(mlh_ctx* ctx, const void* dev_matrix, uint32_t l
   HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, ctx->small, 16, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   memcpy(out, ctx->pinned, 16);
+  return MLH_OK;
+}
+
+// ---- a lookup's multiplicities, before the first commitment (trace_lookup.hip) ----
+
+static bool lookup_columns_ok(uint32_t width, uint32_t value_mask, uint32_t T, uint32_t C) {
+  return width >= 1 && width <= kCsMaxWidth && value_mask && (width == 32 || !(value_mask >> width)) &&
+         T < width && C < width && T != C && !((value_mask >> T) & 1u) && !((value_mask >> C) & 1u);
+}
+
+mlh_status mlh_trace_lookup_counts_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                          uint32_t width, uint32_t value_column_mask,
+                                          uint32_t table_column, uint32_t count_column,
+                                          uint64_t* n_missing, uint64_t* first_missing_row,
+                                          uint32_t log_slots, uint32_t hash_bits,
+                                          uint32_t max_blocks, uint32_t flags) {
+  if (!ctx || !dev_matrix || !n_missing || !first_missing_row || log_height > kLkMaxLogHeight ||
+      !lookup_columns_ok(width, value_column_mask, table_column, count_column) ||
+      log_slots < log_height || log_slots > kLkMaxLogSlots || hash_bits > log_slots ||
+      (flags & ~kLkNoAggregate))
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_lookup_counts: bad argument");
+  PoolBuf scratch(ctx);  // the counters and the slot array
+  MLH_TRY(scratch.alloc(lk_scratch_bytes(log_slots)));
+  LookupArgs a{};
+  a.m = reinterpret_cast<fe*>(dev_matrix);
+  a.log_height = log_height;
+  a.width = width;
+  a.value_mask = value_column_mask;
+  a.table_column = table_column;
+  a.count_column = count_column;
+  a.log_slots = log_slots;
+  a.hash_bits = hash_bits;
+  a.max_blocks = max_blocks;
+  a.flags = flags;
+  ProfScope ps(ctx, "trace_lookup_counts");
+  HIP_TRY(ctx, launch_lookup_insert(a, scratch.p, ctx->stream));
+  HIP_TRY(ctx, launch_lookup_count(a, ctx->stream));
+  ps.end();
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, a.counters, sizeof(LookupCounters),
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  LookupCounters c;
+  memcpy(&c, ctx->pinned, sizeof(c));
+  *n_missing = c.n_missing;
+  *first_missing_row = c.first_missing_row == kLkEmpty ? UINT64_MAX : c.first_missing_row;
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_lookup_counts(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                   uint32_t width, uint32_t value_column_mask,
+                                   uint32_t table_column, uint32_t count_column,
+                                   uint64_t* n_missing, uint64_t* first_missing_row) {
+  const uint32_t log_slots = lk_default_log_slots(log_height);
+  return mlh_trace_lookup_counts_shaped(ctx, dev_matrix, log_height, width, value_column_mask,
+                                        table_column, count_column, n_missing, first_missing_row,
+                                        log_slots, log_slots, 0, 0);
+}
+
+mlh_status mlh_trace_lookup_counts_launch_info(uint32_t log_height, uint32_t n_value_columns,
+                                               uint32_t* threads, uint32_t* blocks,
+                                               uint32_t* log_slots) {
+  if (!threads || !blocks || !log_slots || log_height > kLkMaxLogHeight || n_value_columns < 1 ||
+      n_value_columns > kCsMaxWidth - 2)
+    return MLH_ERR_INVALID;
+  *threads = kLkThreads;
+  *blocks = lk_blocks((uint64_t)n_value_columns << log_height, 0);
+  *log_slots = lk_default_log_slots(log_height);
   return MLH_OK;
 }
 
