@@ -92,6 +92,14 @@ __device__ __forceinline__ void fe_store_at(fe* ubase, Off lane_bytes, const fe&
 // instruction) before a block's accesses keeps each extension local.
 __device__ __forceinline__ void pin_lane_offset(uint32_t& v) { asm("" : "+v"(v)); }
 __device__ __forceinline__ void pin_lane_offset(uint64_t&) {}
+// The constant of the butterflies' wrap correction (bfly_asm.hpp: a "v"
+// operand of every statement).  Passed as a literal, each statement gets a
+// v_mov_b32 of its own; redefined in place once, it is a value the optimiser
+// cannot see through, held in one VGPR for the whole kernel.
+__device__ __forceinline__ uint32_t pin_constant(uint32_t v) {
+  asm("" : "+v"(v));
+  return v;
+}
 constexpr uint32_t bitrev_c(uint32_t x, int bits) {
   uint32_t r = 0;
   for (int i = 0; i < bits; ++i) r |= ((x >> i) & 1u) << (bits - 1 - i);
@@ -227,6 +235,8 @@ __device__ __forceinline__ void ntt_pass_body(const fe* in, fe* out, const fe* _
 #endif
 
   const int tid = threadIdx.x;
+  // - 0x2D00, limb 1 of the butterflies' wrap correction
+  const uint32_t kneg = pin_constant(0xFFFFD300u);
   // kDirect: phase 1 with column cA = tid / TPC and t = bitrev(tid mod TPC),
   // so lane l of a column loads row rev(8t + e) = rev3(e) TPC + l (consecutive
   // across lanes); the first exchange switches to c = tid mod 8, t = tid / 8
@@ -398,13 +408,13 @@ __device__ __forceinline__ void ntt_pass_body(const fe* in, fe* out, const fe* _
           const fe* w0 = tw + 4 * (bj[b] << (LOGR - 1 - s));
           const fe* w1 = tw + 4 * (bj[b + 1] << (LOGR - 1 - s));
           if (!btriv[b] && !btriv[b + 1])
-            bfly_mm_s(u0, v0, w0[0], w0[1], w0[2], w0[3], u1, v1, w1[0], w1[1], w1[2], w1[3], rare);
+            bfly_mm_s(u0, v0, w0[0], w0[1], w0[2], w0[3], u1, v1, w1[0], w1[1], w1[2], w1[3], kneg, rare);
           else if (!btriv[b])
-            bfly_mt_s(u0, v0, w0[0], w0[1], w0[2], w0[3], u1, v1, rare);
+            bfly_mt_s(u0, v0, w0[0], w0[1], w0[2], w0[3], u1, v1, kneg, rare);
           else if (!btriv[b + 1])
-            bfly_mt_s(u1, v1, w1[0], w1[1], w1[2], w1[3], u0, v0, rare);
+            bfly_mt_s(u1, v1, w1[0], w1[1], w1[2], w1[3], u0, v0, kneg, rare);
           else
-            bfly_tt_v(u0, v0, u1, v1, rare);
+            bfly_tt_v(u0, v0, u1, v1, kneg, rare);
         } else {
 #if MLH_LDS_TW
           const fe* w0 = lds_tw + 4 * (bj[b] << (LOGR - 1 - s));
@@ -413,7 +423,7 @@ __device__ __forceinline__ void ntt_pass_body(const fe* in, fe* out, const fe* _
           const fe* w0 = tw + 4 * (bj[b] << (LOGR - 1 - s));
           const fe* w1 = tw + 4 * (bj[b + 1] << (LOGR - 1 - s));
 #endif
-          bfly_mm_v(u0, v0, w0[0], w0[1], w0[2], w0[3], u1, v1, w1[0], w1[1], w1[2], w1[3], rare);
+          bfly_mm_v(u0, v0, w0[0], w0[1], w0[2], w0[3], u1, v1, w1[0], w1[1], w1[2], w1[3], kneg, rare);
         }
       }
     }

@@ -20,19 +20,29 @@ multiples B_k = w * 2^(32k) mod M ("expanded" stage twiddles, fe_mul_pre):
     (x2 < 2^16: probability ~2^-17) is flagged (E: true s = s + 2^96).
   * a = u + s: a carry out of 2^128 (C1) is worth + C, a 46-bit constant,
     which is added to limbs 0 and 1 only; limbs 2 and 3 of the first sum are
-    final.  The carry out of limb 1 (low64 + C >= 2^64: ~2^-18.5 for the
-    values a transform carries) is flagged (FA: true a = a + 2^64).
-  * d = u - s: borrow (B1) -> - C on limbs 0 and 1; the borrow out of limb 1
-    is flagged (FD: true d = d - 2^64).
-  55 VALU per butterfly with a twiddle (31 product, 5 fold, 3 s, 8 u +- s,
-  8 corrections), 16 without, no s_nop in the paired variants.
-The flags are SGPR lane masks; the C++ wrapper checks them with SALU ops and
-fixes flagged lanes on a cold path that adds the lost ripples back in relaxed
+    final.  + C = - 1 + 0x2D00 2^32 takes three instructions: limb 0 minus
+    C1 as a borrow-in, a select of - 0x2D00 (0xFFFFD300, operand kneg) or 0,
+    limb 1 minus that and the borrow.  The carry out of limb 1 (low64 + C >=
+    2^64: ~2^-18.5 for the values a transform carries) happened exactly when
+    C1 is set and the last borrow-out is clear: one s_andn2_b64 gives the
+    flag (FA: true a = a + 2^64).
+  * d = u - s: borrow (B1) -> - C on limbs 0 and 1 by the mirror image (two
+    v_addc and the same select); the borrow out of limb 1 is B1 and not the
+    last carry-out (FD: true d = d - 2^64).
+  53 VALU per butterfly with a twiddle (31 product, 5 fold, 3 s, 8 u +- s,
+  6 corrections), 14 without, no s_nop in the paired variants.
+The flags are SGPR lane masks; the C++ wrapper ORs them on the SALU and
+branches to a cold path that adds the lost ripples back in relaxed
 arithmetic: a += FA*2^64 + E*2^96, d -= FD*2^64 + E*2^96, where a wrap out of
-2^128 is worth +-C (and that C may wrap once more).  A flag set in a wave
-costs that wave one divergent branch: at 2^-17 per lane a few hundred waves
-per 2^24-point pass take it.  The fixes do not depend on how often the flags
-fire, only the time does.
+2^128 is worth +-C (and that C may wrap once more).  The cold path is a
+generated statement too (kinds 'x' and 'y', fix_prog / prod_fix_prog: the
+limbs are in/out operands and the work runs under an EXEC mask built from
+the flags), so that the block the branch enters leaves every value in the
+register it has and the compiler needs no copies where it rejoins the hot
+path; fix() / prod_fix() below and bfly_fix / prod_fix in the header say in
+plain arithmetic what it computes.  At 2^-17 per lane a few hundred waves
+per 2^24-point pass take the branch.  The fixes do not depend on how often
+the flags fire, only the time does.
 
 Products alone ('p': v <- w v by expanded multiples, any twiddle, 41 VALU;
 'f': v <- w v by a plain table entry, 60 VALU) keep the carry into limb 3,
@@ -67,6 +77,7 @@ C = (1 << 128) - M
 MASK32 = (1 << 32) - 1
 KC1 = C >> 32  # 0x2CFF
 K2D00 = 0x2D00
+KNEG = (-K2D00) & MASK32  # 0xFFFFD300: limb 1 of the wrap correction, negated
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "multilinear_amd", "csrc", "bfly_asm.hpp")
@@ -82,8 +93,11 @@ class Ins:
     """One instruction.  dst/src name virtual registers (str) or immediates (int).
     A pair is ('pair', lo, hi).  sdst/cin name SGPR-pair virtual registers."""
 
-    def __init__(self, op, dst, src, sdst=None, cin=None, tag=0, after=()):
+    def __init__(self, op, dst, src, sdst=None, cin=None, tag=0, after=(), sin=()):
         self.op, self.dst, self.src, self.sdst, self.cin, self.tag = op, dst, src, sdst, cin, tag
+        # SGPR-pair sources of a SALU instruction ('sandn2': sdst = sin[0] AND NOT
+        # sin[1]; 'sor': OR; 'saveexec': sdst = EXEC, EXEC &= sin[0]; 'restexec': EXEC = sin[0])
+        self.sin = tuple(sin)
         # names whose every read must precede this instruction (it reuses
         # their register: the second hi partner of a pair's lo, see allocate)
         self.after = tuple(after)
@@ -103,7 +117,10 @@ class Ins:
         return [self.dst] if self.dst else []
 
     def sreads(self):
-        return [self.cin] if self.cin else []
+        return ([self.cin] if self.cin else []) + list(self.sin)
+
+    def is_salu(self):
+        return self.op in ("sandn2", "sor", "saveexec", "restexec")
 
     def swrites(self):
         return [self.sdst] if self.sdst and self.sdst != "junk" else []
@@ -250,12 +267,79 @@ def canon_prog(E, p, b):
         E("cnd", "d%d_%d" % (b, i), [V[i], T[i]], cin=p + "e3")
 
 
+def wrap_rounds(E, p, tag, cur, wrap, out, sub):
+    """Two rounds of "a wrap out of 2^128 is worth C": cur (four limb names)
+    + C (- C with sub) where the SGPR mask wrap is set, then once more on
+    the carry (borrow) of that; the second cannot wrap again.  The last
+    round writes the names in out.  Returns nothing: out holds the result."""
+    first, nxt = ("sub", "subb") if sub else ("add", "addc")
+    for r in (1, 2):
+        new = out if r == 2 else [p + "%s%d_%d" % (tag, r, i) for i in range(4)]
+        cy = [p + "f%s%d_%d" % (tag, r, i) for i in range(4)]
+        m0, m1 = p + "m%s%d_0" % (tag, r), p + "m%s%d_1" % (tag, r)
+        E("cnd", m0, [0, -1], cin=wrap)
+        E("cnd", m1, [0, p + "kc"], cin=wrap)
+        E(first, new[0], [cur[0], m0], sdst=cy[0])
+        E(nxt, new[1], [cur[1], m1], sdst=cy[1], cin=cy[0])
+        E(nxt, new[2], [cur[2], 0], sdst=cy[2], cin=cy[1])
+        E(nxt, new[3], [cur[3], 0], sdst=cy[3] if r == 1 else "junk", cin=cy[2])
+        cur, wrap = new, cy[3]
+
+
+def fix_prog(E, p, b):
+    """Kind 'x', the butterflies' cold path as a statement: (a, d) <-
+    fix(a, d, fe, fa, fd) with the three flags as SGPR lane masks (inputs sE,
+    sFA, sFD).  The butterfly's limbs are in/out operands, so the block that
+    holds this statement defines them in the registers they already have.
+    Runs under EXEC = EXEC AND (fe OR fa OR fd): the other lanes keep their
+    values.  a += fa 2^64 + fe 2^96, d -= fd 2^64 + fe 2^96, then the two
+    possible re-wraps of relaxed_add / relaxed_sub.  Emitted in program order
+    (its cost is paid by a few hundred waves per pass)."""
+    U = ["u%d_%d" % (b, i) for i in range(4)]
+    V = ["v%d_%d" % (b, i) for i in range(4)]
+    fe, fa, fd = "sE%d" % b, "sFA%d" % b, "sFD%d" % b
+    E("sor", None, [], sdst=p + "em0", sin=[fe, fa])
+    E("sor", None, [], sdst=p + "em1", sin=[p + "em0", fd])
+    E("saveexec", None, [], sdst=p + "esave", sin=[p + "em1"])
+    E("cnd", p + "ya", [0, 1], cin=fa)
+    E("cnd", p + "yd", [0, 1], cin=fd)
+    E("cnd", p + "ye", [0, 1], cin=fe)
+    E("mov", p + "kc", [KC1])
+    for tag, X, y2, sub in (("a", U, p + "ya", False), ("d", V, p + "yd", True)):
+        first, nxt = ("sub", "subb") if sub else ("add", "addc")
+        cur = [X[0], X[1], p + tag + "0_2", p + tag + "0_3"]
+        E(first, cur[2], [X[2], y2], sdst=p + "f%s0_2" % tag)
+        E(nxt, cur[3], [X[3], p + "ye"], sdst=p + "f%s0_3" % tag, cin=p + "f%s0_2" % tag)
+        wrap_rounds(E, p, tag, cur, p + "f%s0_3" % tag, ["%s%d_%d" % (tag, b, i) for i in range(4)], sub)
+    E("restexec", None, [], sin=[p + "esave"])
+
+
+def prod_fix_prog(E, p, b):
+    """Kind 'y', the products' cold path as a statement (as fix_prog):
+    v <- v + fk C - fg 2^64 in relaxed arithmetic, flags sK and sG."""
+    V = ["v%d_%d" % (b, i) for i in range(4)]
+    fk, fg = "sK%d" % b, "sG%d" % b
+    E("sor", None, [], sdst=p + "em0", sin=[fk, fg])
+    E("saveexec", None, [], sdst=p + "esave", sin=[p + "em0"])
+    E("cnd", p + "yg", [0, 1], cin=fg)
+    E("mov", p + "kc", [KC1])
+    K = [p + "k%d" % i for i in range(4)]
+    wrap_rounds(E, p, "k", V, fk, K, False)
+    cur = [K[0], K[1], p + "s0_2", p + "s0_3"]
+    E("sub", cur[2], [K[2], p + "yg"], sdst=p + "fs0_2")
+    E("subb", cur[3], [K[3], 0], sdst=p + "fs0_3", cin=p + "fs0_2")
+    wrap_rounds(E, p, "s", cur, p + "fs0_3", ["d%d_%d" % (b, i) for i in range(4)], True)
+    E("restexec", None, [], sin=[p + "esave"])
+
+
 def bfly_prog(b, kind):
     """Instruction list of butterfly b.  kind 'm': with a stage twiddle, 't':
     trivial (w = 1), 'p': product only v <- w v (safe first mads; any twiddle).
     Operand names: u{b}_{i} (in, tied to a), v{b}_{i} (in, tied to d),
-    B{b}_{k}{j} (twiddle limbs), kc1 (VGPR 0x2CFF), k2d00 (SGPR 0x2D00).
-    Flags E{b}, FA{b}, FD{b}; K{b}, G{b} for the products alone."""
+    B{b}_{k}{j} (twiddle limbs), kneg (VGPR 0xFFFFD300; kc1, 0x2CFF, in kind
+    'c'), k2d00 (SGPR 0x2D00).  Flags E{b}, FA{b}, FD{b}; K{b}, G{b} for the
+    products alone.  Kinds 'x' and 'y' are the cold paths (fix_prog,
+    prod_fix_prog), whose flags are inputs sE{b}, sFA{b}, sFD{b} / sK{b}, sG{b}."""
     p = "b%d." % b
     U = ["u%d_%d" % (b, i) for i in range(4)]
     V = ["v%d_%d" % (b, i) for i in range(4)]
@@ -263,6 +347,12 @@ def bfly_prog(b, kind):
     E = lambda *a, **k: prog.append(Ins(*a, tag=b, **k))
     if kind == "c":
         canon_prog(E, p, b)
+        return prog
+    if kind == "x":
+        fix_prog(E, p, b)
+        return prog
+    if kind == "y":
+        prod_fix_prog(E, p, b)
         return prog
     if kind == "f":
         W = ["W%d_%d" % (b, j) for j in range(4)]
@@ -300,25 +390,37 @@ def bfly_prog(b, kind):
     for i in (1, 2, 3):
         E("addc", A[i], [U[i], S[i]], sdst=p + ("f%d" % i if i < 3 else "C1"), cin=p + "f%d" % (i - 1))
         E("subb", D[i], [U[i], S[i]], sdst=p + ("g%d" % i if i < 3 else "B1"), cin=p + "g%d" % (i - 1))
-    # a + C1*C, d - B1*C   (C = 0x2CFF_FFFFFFFF) on limbs 0 and 1 only
-    E("cnd", p + "ma0", [0, -1], cin=p + "C1")
-    E("cnd", p + "ma1", [0, "kc1"], cin=p + "C1")
-    E("cnd", p + "md0", [0, -1], cin=p + "B1")
-    E("cnd", p + "md1", [0, "kc1"], cin=p + "B1")
-    E("add", aout[0], [A[0], p + "ma0"], sdst=p + "h0")
-    E("sub", dout[0], [D[0], p + "md0"], sdst=p + "i0")
-    E("addc", aout[1], [A[1], p + "ma1"], sdst="FA%d" % b, cin=p + "h0")
-    E("subb", dout[1], [D[1], p + "md1"], sdst="FD%d" % b, cin=p + "i0")
+    # a + C1*C, d - B1*C on limbs 0 and 1 only, C = 0x2D00*2^32 - 1: the - 1 is
+    # the wrap flag itself taken as a borrow-in (carry-in on the d side), and
+    # the 0x2D00 goes into limb 1 as minus its negative, so each side is two
+    # carry instructions and one select.  Limb 1 carried out (borrowed, for d)
+    # exactly when the wrap flag is set and the second instruction's
+    # borrow-out (carry-out) is clear: one SALU and-not per side.
+    E("subb", aout[0], [A[0], 0], sdst=p + "h0", cin=p + "C1")
+    E("addc", dout[0], [D[0], 0], sdst=p + "i0", cin=p + "B1")
+    E("cnd", p + "ma", [0, "kneg"], cin=p + "C1")
+    E("cnd", p + "md", [0, "kneg"], cin=p + "B1")
+    E("subb", aout[1], [A[1], p + "ma"], sdst=p + "h1", cin=p + "h0")
+    E("addc", dout[1], [D[1], p + "md"], sdst=p + "i1", cin=p + "i0")
+    E("sandn2", None, [], sdst="FA%d" % b, sin=[p + "C1", p + "h1"])
+    E("sandn2", None, [], sdst="FD%d" % b, sin=[p + "B1", p + "i1"])
     return prog
 
 
 # ------------------------------------------------------------- scheduling ---
 
 SGPR_GAP = 3  # consumer index - producer index >= 3: two wait states between
+# A SALU read of an SGPR pair that a VALU wrote needs no wait state on gfx950:
+# the manual wait-state table of the CDNA3/CDNA4 ISA lists VALU-written SGPRs
+# only against VALU (2), VMEM (5) and v_readlane/v_writelane lane-select (4)
+# readers, and the SALU interlocks on its own (hipcc itself emits
+# v_cmp -> s_and_b64 back to back).  Nor does a VALU read of a SALU-written
+# SGPR need one.
+SALU_GAP = 1
 
 
-def schedule(progs):
-    """List-schedule the union of independent instruction lists.  Dependencies:
+def schedule(progs, in_order=False):
+    """in_order: program order, padded where a dependency asks for it.  Otherwise list-schedule the union of independent instruction lists.  Dependencies:
     true (RAW) on VGPRs (no gap) and SGPRs (SGPR_GAP), plus program order
     between writes/reads of tied output operands.  Priority: longest path."""
     ins = [i for p in progs for i in p]
@@ -332,7 +434,8 @@ def schedule(progs):
                 deps[idx].append((writer[r], 1))
             readers.setdefault(r, []).append(idx)
         for r in it.sreads():
-            deps[idx].append((writer[r], SGPR_GAP))
+            if r in writer:  # (not a flag handed in as an operand)
+                deps[idx].append((writer[r], SALU_GAP if it.is_salu() or ins[writer[r]].is_salu() else SGPR_GAP))
         for w in it.vwrites() + it.swrites():
             writer[w] = idx
     # tied outputs: a{b}_i overwrites u{b}_i, d{b}_i overwrites v{b}_i -> after every read
@@ -361,7 +464,7 @@ def schedule(progs):
     remaining = set(range(n))
     t = 0
     while remaining:
-        ready = [i for i in remaining if all(p in done_at and t - done_at[p] >= g for p, g in deps[i])]
+        ready = [i for i in ([min(remaining)] if in_order else remaining) if all(p in done_at and t - done_at[p] >= g for p, g in deps[i])]
         if not ready:
             order.append(None)
             t += 1
@@ -477,18 +580,19 @@ def emit(kinds, bsrc):
     bsrc: 's' (twiddle limbs in SGPRs) or 'v'.  Returns (asm lines, operand
     description, nvgpr, nsgpr-pairs)."""
     progs = [bfly_prog(b, k) for b, k in enumerate(kinds)]
-    ins, order = schedule(progs)
+    ins, order = schedule(progs, in_order=kinds[0] in "xy")
     seq, assign, nv, ns = allocate(ins, order)
     # trailing pad: the C++ code may read the flag SGPRs with a VALU right away
+    # (the flags a SALU instruction wrote need none)
     tail = 0
     for back, it in enumerate(reversed(seq)):
-        if it is not None and any(s.startswith(("K", "G", "E", "FA", "FD")) for s in it.swrites()):
+        if it is not None and not it.is_salu() and any(s.startswith(("K", "G", "E", "FA", "FD")) for s in it.swrites()):
             tail = max(tail, SGPR_GAP - 1 - back)
     return seq, assign, nv, ns, max(tail, 0)
 
 
 def has_u(k):
-    return k in ("m", "t")
+    return k in ("m", "t", "x")
 
 
 def operand_names(kinds):
@@ -511,14 +615,20 @@ def operand_names(kinds):
             flags.append("E%d" % b)
         if k in ("p", "f"):
             flags += ["K%d" % b, "G%d" % b]
-        if has_u(k):
+        if k in ("m", "t"):
             flags += ["FA%d" % b, "FD%d" % b]
     for b, k in enumerate(kinds):
         if k in ("m", "p"):
             ins += ["B%d_%d%d" % (b, kk, j) for kk in range(4) for j in range(4)]
         if k == "f":
             ins += ["W%d_%d" % (b, j) for j in range(4)]
-    if any(k in ("m", "t", "c") for k in kinds):
+        if k == "x":
+            ins += ["sE%d" % b, "sFA%d" % b, "sFD%d" % b]
+        if k == "y":
+            ins += ["sK%d" % b, "sG%d" % b]
+    if any(k in ("m", "t") for k in kinds):
+        ins += ["kneg"]
+    if any(k == "c" for k in kinds):
         ins += ["kc1"]
     if any(k in ("m", "p", "f") for k in kinds):
         ins += ["k2d00"]
@@ -568,6 +678,11 @@ def render(kinds, bsrc):
         if it is None:
             lines.append("s_nop 0")
             continue
+        # register classes: a temporary's name decides its class (is_sgpr_name)
+        for r in it.vreads() + it.vwrites():
+            assert not isinstance(assign.get(r), tuple), ("SGPR temporary as a VALU operand", r)
+        for r in it.sreads() + it.swrites():
+            assert not isinstance(assign.get(r), str), ("VGPR temporary as a mask", r)
         sd = name(it.sdst) if it.sdst else None
         if it.op == "mad":
             s2 = pname(it.src[2]) if isinstance(it.src[2], tuple) else "0"
@@ -593,6 +708,14 @@ def render(kinds, bsrc):
                                                                name(it.src[1]), name(it.cin)))
         elif it.op == "mov":
             lines.append("v_mov_b32 %s, %s" % (name(it.dst), name(it.src[0])))
+        elif it.op == "sandn2":
+            lines.append("s_andn2_b64 %s, %s, %s" % (sd, name(it.sin[0]), name(it.sin[1])))
+        elif it.op == "sor":
+            lines.append("s_or_b64 %s, %s, %s" % (sd, name(it.sin[0]), name(it.sin[1])))
+        elif it.op == "saveexec":
+            lines.append("s_and_saveexec_b64 %s, %s" % (sd, name(it.sin[0])))
+        elif it.op == "restexec":
+            lines.append("s_mov_b64 exec, %s" % name(it.sin[0]))
         else:
             raise ValueError(it.op)
     if tail:
@@ -629,6 +752,26 @@ def emulate(lines, env):
         a = [s.strip() for s in rest.split(",")] if rest else []
         if op == "s_nop":
             continue
+        if op == "s_andn2_b64":
+            regs[a[0]] = regs[a[1]] & ~regs[a[2]] & 1
+            continue
+        if op == "s_or_b64":
+            regs[a[0]] = regs[a[1]] | regs[a[2]]
+            continue
+        if op == "s_and_saveexec_b64":
+            # (both operands are read before the destination is written: they may be one pair)
+            regs[a[0]], regs["exec"] = regs.get("exec", 1), regs.get("exec", 1) & regs[a[1]]
+            continue
+        if op == "s_mov_b64":
+            assert a[0] == "exec"
+            regs["exec"] = regs[a[1]]
+            continue
+        if not regs.get("exec", 1):
+            # an inactive lane: no VGPR write, and a zero bit in a carry-out mask
+            if op in ("v_mad_u64_u32", "v_addc_co_u32_e64", "v_add_co_u32_e64", "v_subb_co_u32_e64",
+                      "v_sub_co_u32_e64"):
+                regs[a[1]] = 0
+            continue
         if op == "v_mad_u64_u32":
             v = rd(a[2]) * rd(a[3]) + rdp(a[4])
             wrp(a[0], v)
@@ -655,8 +798,11 @@ def emulate(lines, env):
 
 
 def check_hazards(lines):
-    """Every VALU read of an SGPR written by a VALU must be >= 2 wait states later."""
+    """Every VALU read of an SGPR written by a VALU must be >= 2 wait states
+    later; a SALU read of it, or a read of what a SALU wrote, needs none
+    (SALU_GAP)."""
     last_w = {}
+    salu_w = set()
     t = 0
     for ln in lines:
         op, _, rest = ln.partition(" ")
@@ -672,11 +818,24 @@ def check_hazards(lines):
         if op in ("v_mad_u64_u32", "v_addc_co_u32_e64", "v_add_co_u32_e64", "v_subb_co_u32_e64",
                   "v_sub_co_u32_e64"):
             writes.append(a[1])
+        salu = op.startswith("s_")
+        if op in ("s_andn2_b64", "s_or_b64"):
+            reads += [a[1], a[2]]
+            writes.append(a[0])
+        elif op == "s_and_saveexec_b64":  # (EXEC written by the SALU: no wait state before a VALU)
+            reads.append(a[1])
+            writes.append(a[0])
+        elif op == "s_mov_b64":
+            reads.append(a[1])
+        elif salu:
+            raise ValueError(op)
         for r in reads:
-            if r in last_w and t - last_w[r] < SGPR_GAP:
+            gap = SALU_GAP if salu or r in salu_w else SGPR_GAP
+            if r in last_w and t - last_w[r] < gap:
                 raise AssertionError("SGPR hazard on %s at '%s' (distance %d)" % (r, ln, t - last_w[r]))
         for w in writes:
             last_w[w] = t
+            (salu_w.add if salu else salu_w.discard)(w)
         t += 1
 
 
@@ -707,6 +866,8 @@ def run_regs(kinds, lines, opn, uvals, vvals, wvals):
                 env["%%%d" % opn["W%d_%d" % (b, j)]] = limbs(wvals[b])[j]
     if "kc1" in opn:
         env["%%%d" % opn["kc1"]] = KC1
+    if "kneg" in opn:
+        env["%%%d" % opn["kneg"]] = KNEG
     if "k2d00" in opn:
         env["%%%d" % opn["k2d00"]] = K2D00
     return emulate(lines, env)
@@ -734,6 +895,66 @@ def run_case(kinds, lines, opn, nv, uvals, vvals, wvals):
         a, d = fix(a, d, fe, fa, fd)
         res.append((a, d))
     return res
+
+
+def run_fix(lines, opn, a, d, fe, fa, fd, active=1):
+    """Emulate one lane of the fix statement (kind 'x'); active: the lane's
+    EXEC bit on entry.  Returns (a, d, EXEC bit on exit)."""
+    env = {"exec": active}
+    for i in range(4):
+        env["%%%d" % opn["u0_%d" % i]] = limbs(a)[i]
+        env["%%%d" % opn["v0_%d" % i]] = limbs(d)[i]
+    for nm, f in (("sE0", fe), ("sFA0", fa), ("sFD0", fd)):
+        env["%%%d" % opn[nm]] = f
+    regs = emulate(lines, env)
+    return (value([regs["%%%d" % opn["u0_%d" % i]] for i in range(4)]),
+            value([regs["%%%d" % opn["v0_%d" % i]] for i in range(4)]), regs["exec"])
+
+
+def run_prod_fix(lines, opn, v, fk, fg, active=1):
+    """As run_fix for the products' statement (kind 'y'): (v, EXEC bit on exit)."""
+    env = {"exec": active, "%%%d" % opn["sK0"]: fk, "%%%d" % opn["sG0"]: fg}
+    for i in range(4):
+        env["%%%d" % opn["v0_%d" % i]] = limbs(v)[i]
+    regs = emulate(lines, env)
+    return value([regs["%%%d" % opn["v0_%d" % i]] for i in range(4)]), regs["exec"]
+
+
+def prod_fix(v, fk, fg):
+    """The products' cold path (C++ prod_fix): + C for fk, then - 2^64 for fg."""
+    return relaxed_sub(relaxed_add(v, fk << 128), fg << 64)
+
+
+def fix_operands():
+    """Operands for the cold-path statements: around 0 and 2^128 at the
+    distances the add-backs and their re-wraps turn on (2^64, 2^96, C)."""
+    top = (1 << 128) - 1
+    out = [0, 1, top, (1 << 64) - 1, 1 << 64, (1 << 96) - 1, 1 << 96, (1 << 96) + (1 << 64) - 1, (1 << 96) + (1 << 64)]
+    for base in (0, 1 << 64, 1 << 96, (1 << 96) + (1 << 64), C, 2 * C):
+        for off in (-1, 0, 1):
+            out += [(top + 1 - base + off) % (1 << 128), (base + off) % (1 << 128)]
+    return sorted(set(out))
+
+
+def fix_selftest(kind, lines, opn, trials=200, seed=3):
+    """The cold-path statements against fix() / prod_fix(): every flag
+    combination on random and edge operands, active and inactive lanes."""
+    rng = random.Random(seed)
+    edge = fix_operands()
+    n = 0
+    for t in range(trials):
+        a = rng.choice(edge) if rng.random() < 0.5 else rng.randrange(1 << 128)
+        d = rng.choice(edge) if rng.random() < 0.5 else rng.randrange(1 << 128)
+        for f in range(8 if kind == "x" else 4):
+            fe, fa, fd = f & 1, (f >> 1) & 1, f >> 2
+            if kind == "x":
+                assert run_fix(lines, opn, a, d, fe, fa, fd) == fix(a, d, fe, fa, fd) + (1,), (a, d, fe, fa, fd)
+                assert run_fix(lines, opn, a, d, fe, fa, fd, active=0) == (a, d, 0), (a, d, fe, fa, fd)
+            else:
+                assert run_prod_fix(lines, opn, d, fe, fa) == (prod_fix(d, fe, fa), 1), (d, fe, fa)
+                assert run_prod_fix(lines, opn, d, fe, fa, active=0) == (d, 0), (d, fe, fa)
+            n += 1
+    return n
 
 
 def relaxed_add(x, y):
@@ -840,6 +1061,30 @@ VARIANTS = [("m", "m"), ("m",), ("t", "t"), ("t",), ("m", "t"), ("p", "p"), ("p"
             ("c", "c", "c", "c"), ("c",)]
 
 
+def cxx_fix(kind):
+    """The cold-path statement as a function: kind 'x' bfly_fix_asm, 'y' prod_fix_asm."""
+    lines, outs, flags, ins, ns, nv, opn = render((kind,), "v")
+    assert not flags
+    cname = {"u": "a", "v": "d" if kind == "x" else "v"}
+    ol = ['"+v"(%s.w[%s])' % (cname[o[0]], o.split("_")[1]) for o in outs]
+    ol += ['"=&s"(st[%d])' % s for s in range(ns)] + ['"=&s"(junk)']
+    arg = {"sE0": "fe_", "sFA0": "fa", "sFD0": "fd", "sK0": "fk", "sG0": "fg"}
+    il = ['"s"(%s)' % arg[i] for i in ins]
+    clob = ", ".join(['"v%d"' % (VBASE + r) for r in range(nv)] + ['"scc"'])
+    stats = "%d VALU, %d s_nop, %d VGPR temps, %d SGPR-pair temps" % (
+        sum(1 for l in lines if l.startswith("v_")), sum(1 for l in lines if l.startswith("s_nop")), nv, ns)
+    head = ("bfly_fix_asm(fe& a, fe& d, uint64_t fe_, uint64_t fa, uint64_t fd)" if kind == "x" else
+            "prod_fix_asm(fe& v, uint64_t fk, uint64_t fg)")
+    code = ("// %s as one statement, on the lanes a flag names: the limbs are in/out\n"
+            "// operands, so the rare-case block leaves them in the registers they have.\n// %s\n"
+            "__device__ __forceinline__ void %s {\n"
+            "  uint64_t st[%d];\n  uint64_t junk;\n"
+            '  asm volatile(\n      "%s"\n      : %s\n      : %s\n      : %s);\n}\n') % (
+        "bfly_fix" if kind == "x" else "prod_fix", stats, head, ns, "\\n\\t".join(lines), ",\n        ".join(ol),
+        ",\n        ".join(il), clob)
+    return code, lines, opn
+
+
 def cxx_function(kinds, bsrc):
     lines, outs, flags, ins, ns, nv, opn = render(kinds, bsrc)
     fname = "bfly_%s_%s" % ("".join(kinds), bsrc)
@@ -851,8 +1096,14 @@ def cxx_function(kinds, bsrc):
             args += ["const fe& B%d_%d" % (b, k) for k in range(4)]
         if kinds[b] == "f":
             args.append("const fe& W%d" % b)
+    # the corrections' constant: a parameter, so that a kernel holds it in one
+    # VGPR for all its statements; the overload without it passes the literal
+    kconst = [(k, v) for k, v in (("kneg", KNEG), ("kc1", KC1)) if k in ins]
+    thin_args = list(args)
+    args += ["uint32_t %s" % k for k, _ in kconst]
     if flags:
         args += ["uint64_t& rare"]
+        thin_args += ["uint64_t& rare"]
     body = []
     for f in flags:
         body.append("  uint64_t %s;" % f)
@@ -862,8 +1113,6 @@ def cxx_function(kinds, bsrc):
     if ns:
         body.append("  uint64_t st[%d];" % ns)
     body.append("  uint64_t junk;")
-    if "kc1" in ins:
-        body.append("  const uint32_t kc1 = 0x2CFFu;")
     if "k2d00" in ins:
         body.append("  const uint32_t k2d00 = 0x2D00u;")
     asm = "\\n\\t".join(lines)
@@ -878,8 +1127,8 @@ def cxx_function(kinds, bsrc):
     ol.append('"=&s"(junk)')
     il = []
     for i in ins:
-        if i == "kc1":
-            il.append('"v"(kc1)')
+        if i in ("kc1", "kneg"):
+            il.append('"v"(%s)' % i)
         elif i == "k2d00":
             il.append('"s"(k2d00)')
         elif i[0] == "W":
@@ -888,7 +1137,8 @@ def cxx_function(kinds, bsrc):
         else:
             b, kj = i[1:].split("_")
             il.append('"%s"(B%s_%s.w[%s])' % (bsrc, b, kj[0], kj[1]))
-    clob = ", ".join('"v%d"' % (VBASE + r) for r in range(nv))
+    clob = ", ".join(['"v%d"' % (VBASE + r) for r in range(nv)] +
+                     (['"scc"'] if any(l.startswith("s_andn2") for l in lines) else []))
     body.append('  asm volatile(\n      "%s"\n      : %s\n      : %s\n      : %s);' % (
         asm, ",\n        ".join(ol), ",\n        ".join(il), clob))
     for o in outs:
@@ -900,16 +1150,22 @@ def cxx_function(kinds, bsrc):
         body.append("  if (__builtin_expect(rare != 0, 0)) {")
     for b in range(nb):
         if kinds[b] in ("p", "f"):
-            body.append("    prod_fix(v%d, K%d, G%d);" % (b, b, b))
+            body.append("    prod_fix_asm(v%d, K%d, G%d);" % (b, b, b))
         elif kinds[b] != "c":
             fe = "E%d" % b if kinds[b] == "m" else "0ull"
-            body.append("    bfly_fix(u%d, v%d, %s, FA%d, FD%d);" % (b, b, fe, b, b))
+            body.append("    bfly_fix_asm(u%d, v%d, %s, FA%d, FD%d);" % (b, b, fe, b, b))
     if flags:
         body.append("  }")
     stats = "%d VALU, %d s_nop, %d VGPR temps, %d SGPR-pair temps" % (
         sum(1 for l in lines if l.startswith("v_")), sum(1 for l in lines if l.startswith("s_nop")), nv, ns)
-    return fname, "// %s\n__device__ __forceinline__ void %s(%s) {\n%s\n}\n" % (
-        stats, fname, ", ".join(args), "\n".join(body)), lines
+    code = "// %s\n__device__ __forceinline__ void %s(%s) {\n%s\n}\n" % (
+        stats, fname, ", ".join(args), "\n".join(body))
+    if kconst:
+        call = [a.split()[-1] for a in thin_args]
+        call[len(call) - (1 if flags else 0):len(call) - (1 if flags else 0)] = ["0x%Xu" % v for _, v in kconst]
+        code += "__device__ __forceinline__ void %s(%s) {\n  %s(%s);\n}\n" % (
+            fname, ", ".join(thin_args), fname, ", ".join(call))
+    return fname, code, lines
 
 
 HEADER = """// GENERATED by tools/gen_bfly.py -- do not edit by hand.
@@ -972,8 +1228,9 @@ __device__ __forceinline__ fe relaxed_sub(const fe& x, const fe& y) {
   return b ? relaxed_sub_c(t) : t;
 }
 
-// Cold path.  The butterflies leave out the carry ripples that are almost
-// never set and flag the lanes where one was: fa, the carry out of limb 1 of
+// Cold path in plain C++: what the generated bfly_fix_asm / prod_fix_asm below
+// compute (the wrappers call those).  The butterflies leave out the carry
+// ripples that are almost never set and flag the lanes where one was: fa, the carry out of limb 1 of
 // a when it took its + C (true a = a + 2^64); fd, the borrow out of limb 1 of
 // d when it took its - C (true d = d - 2^64); fe, the carry out of limb 2 of
 // s = w v when the top word was folded in (true s = s + 2^96, which a gains
@@ -1004,6 +1261,11 @@ __device__ __forceinline__ fe relaxed_canon(const fe& x) { return canon_with_car
 def main():
     parts = [HEADER]
     total = 0
+    for kind in "xy":
+        code, lines, opn = cxx_fix(kind)
+        check_hazards(lines)
+        total += fix_selftest(kind, lines, opn)
+        parts.append(code)
     for kinds in VARIANTS:
         for bsrc in ("s", "v"):
             if not any(k in ("m", "p") for k in kinds) and bsrc == "s":
