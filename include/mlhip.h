@@ -929,6 +929,85 @@ mlh_status mlh_trace_lookup_counts_shaped(mlh_ctx* ctx, void* dev_matrix, uint32
                                           uint32_t log_slots, uint32_t hash_bits,
                                           uint32_t max_blocks, uint32_t flags);
 
+/* ---- tuple lookups: multi-column multiplicities on the device --------------- *
+ * The lookups of a real trace have tuple keys: a 4-bit XOR table is the triple
+ * (x, y, x ^ y), a tagged range table a pair.  Phase 2 compresses a tuple with
+ * a trace random (a + alpha * b + alpha^2 * c) and inverts gamma - that; the
+ * multiplicity column is pre-random and must count the tuples themselves
+ * (counting per column is wrong: every component of (3, 5, 7) can occur in its
+ * own table column while the triple occurs in no table row).  This is the
+ * owner rule of mlh_trace_lookup_counts with a tuple in place of an element
+ * (DESIGN.md 6h).
+ * Let key(j) = the 16 * arity bytes matrix[j][table_columns[0]] || ... ||
+ * matrix[j][table_columns[arity - 1]]; row j is the owner of its key when no
+ * lower row has the same key.  Let value(i, l) = the same concatenation over
+ * value_columns[l * arity + 0 .. arity - 1] of row i (value_columns is
+ * [n_tuples][arity], tuple-major).  A pair (i, l) is enabled when
+ * selector_columns is NULL, or selector_columns[l] is MLH_LOOKUP_NO_SELECTOR,
+ * or the 16 bytes of matrix[i][selector_columns[l]] are not all zero.  After
+ * the call
+ *   matrix[j][count_column] = the number of enabled pairs (i, l) with
+ *     value(i, l) == key(j), as a canonical element, when j is an owner, and
+ *     zero otherwise (the lowest row of a repeated key takes the whole count);
+ *   *n_missing = the number of enabled pairs whose value equals no key;
+ *   *first_missing_row = the lowest such i, UINT64_MAX when there is none;
+ * and no other column is written.  A missing tuple is no error: MLH_OK, and
+ * the counts of the tuples that were found are right.  A disabled pair is
+ * neither counted nor missing.  The order of the components matters: (x, y)
+ * and (y, x) are different keys.  Equality is equality of the bytes.  The
+ * result is a pure function of the matrix and the column lists: it does not
+ * depend on the launch shape, on where the hash puts a key or on the order of
+ * the atomics.
+ * width 1..32, log_height 0..28, arity 1..MLH_LOOKUP_MAX_ARITY, n_tuples
+ * 1..MLH_LOOKUP_MAX_TUPLES, arity * n_tuples <= 32.  MLH_ERR_INVALID, the
+ * matrix untouched, for anything outside these, a NULL ctx, dev_matrix,
+ * table_columns, value_columns, n_missing or first_missing_row, a column at
+ * or above width (a selector other than MLH_LOOKUP_NO_SELECTOR included), two
+ * equal table columns, a value column that is a table column, and
+ * count_column among the table, value or selector columns.  A value column
+ * may repeat within a tuple and across tuples ((x, y, z) and (y, x, z) of a
+ * commutative table share all three), and a selector may be any column but
+ * the count column.
+ * The hash join of mlh_trace_lookup_counts: the slot array holds row indices,
+ * the hash is MurmurHash3 x86_32 over the 4 * arity limbs in component order
+ * with the length word 16 * arity (at arity 1 the one-column entry's hash),
+ * and a visited slot's row is compared component by component, ending at the
+ * first that differs.  One kernel instance per arity keeps the thread's tuple
+ * in registers; the value and selector columns stand behind the counters in
+ * the 256-byte header of the pooled scratch array, and a wave, whose 64 pairs
+ * are always of one tuple, reads its tuple's with scalar loads.  Both
+ * launches: 256 threads, min(ceil(work / 256), 1024) blocks looping with the
+ * grid's stride, work = 2^log_height rows for the insert and n_tuples *
+ * 2^log_height pairs for the count, log_slots = log_height + 2.  Synchronises
+ * once to return the two counters. */
+#define MLH_LOOKUP_MAX_ARITY 8
+#define MLH_LOOKUP_MAX_TUPLES 16
+#define MLH_LOOKUP_NO_SELECTOR 0xFFFFFFFFu
+mlh_status mlh_trace_lookup_tuple_counts(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                         uint32_t width, uint32_t arity,
+                                         const uint32_t* table_columns, uint32_t n_tuples,
+                                         const uint32_t* value_columns,
+                                         const uint32_t* selector_columns, uint32_t count_column,
+                                         uint64_t* n_missing, uint64_t* first_missing_row);
+/* Its launch shape: threads per block (256), blocks of the count launch
+ * (min(ceil(2^log_height * n_tuples / 256), 1024)) and log_slots (log_height +
+ * 2).  n_tuples 1..16, log_height 0..28. */
+mlh_status mlh_trace_lookup_tuple_counts_launch_info(uint32_t log_height, uint32_t n_tuples,
+                                                     uint32_t* threads, uint32_t* blocks,
+                                                     uint32_t* log_slots);
+/* The same bytes under another shape: log_slots, hash_bits, max_blocks and
+ * flags as mlh_trace_lookup_counts_shaped takes them (flags bit 0 turns the
+ * wave-level combining off, every other bit is MLH_ERR_INVALID). */
+mlh_status mlh_trace_lookup_tuple_counts_shaped(mlh_ctx* ctx, void* dev_matrix,
+                                                uint32_t log_height, uint32_t width,
+                                                uint32_t arity, const uint32_t* table_columns,
+                                                uint32_t n_tuples, const uint32_t* value_columns,
+                                                const uint32_t* selector_columns,
+                                                uint32_t count_column, uint64_t* n_missing,
+                                                uint64_t* first_missing_row, uint32_t log_slots,
+                                                uint32_t hash_bits, uint32_t max_blocks,
+                                                uint32_t flags);
+
 /* ---- multilinear PCS (src/fri/multilinear_pcs.rs) ------------------------ */
 typedef struct mlh_pcs_proof {
   mlh_fri_proof fri;

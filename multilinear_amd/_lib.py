@@ -273,6 +273,15 @@ SIGNATURES = {
     "mlh_trace_lookup_counts_shaped": (_I, [_P, _P, _U32, _U32, _U32, _U32, _U32,
                                             ctypes.POINTER(_U64), ctypes.POINTER(_U64), _U32, _U32,
                                             _U32, _U32]),
+    "mlh_trace_lookup_tuple_counts": (_I, [_P, _P, _U32, _U32, _U32, ctypes.POINTER(_U32), _U32,
+                                           ctypes.POINTER(_U32), ctypes.POINTER(_U32), _U32,
+                                           ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "mlh_trace_lookup_tuple_counts_launch_info": (_I, [_U32, _U32, ctypes.POINTER(_U32),
+                                                       ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "mlh_trace_lookup_tuple_counts_shaped": (_I, [_P, _P, _U32, _U32, _U32, ctypes.POINTER(_U32),
+                                                  _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32),
+                                                  _U32, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                                                  _U32, _U32, _U32, _U32]),
     "mlh_trace_columns_launch_info": (_I, [_U32, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     "mlh_trace_commit": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(_P)]),
     "mlh_trace_commitment_root": (_I, [_P, _P]),

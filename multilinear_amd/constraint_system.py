@@ -20,7 +20,10 @@ ops below on column vectors), and ``prove`` / ``PhasedSystemProof.verify`` are
 mlh_system_prove_phased / _verify_phased, the column sum by default from
 mlh_trace_column_sum.  A lookup's multiplicity column, which is pre-random, is
 counted in place before ``phased_prover`` by ``Trace.lookup_multiplicities``
-(mlh_trace_lookup_counts).
+(mlh_trace_lookup_counts), or, for keys of several columns such as (x, y, x ^ y),
+by ``Trace.lookup_tuple_multiplicities`` (mlh_trace_lookup_tuple_counts);
+``tuple_key`` spells the compressed key of such a lookup for the fill and the
+constraint.
 """
 import ctypes
 import struct
@@ -393,6 +396,110 @@ class Trace:
         if n:
             raise ValueError("%d looked-up value%s not in table column %d, the first in row %d"
                              % (n, "" if n == 1 else "s", table_column, first))
+
+    def lookup_tuple_counts(self, value_tuples, table_columns, count_column, selectors=None,
+                            device=0):
+        """A tuple lookup's multiplicities, in place
+        (mlh_trace_lookup_tuple_counts): the key of a row is its
+        ``table_columns`` in that order, and column ``count_column`` of the
+        lowest row holding each key receives how many enabled (row, tuple)
+        pairs of ``value_tuples`` (each a column list as long as
+        ``table_columns``) hold it, the other rows zero.  ``selectors``: None,
+        or per tuple a column (the pair is enabled where it is nonzero) or
+        None.  Returns (n_missing, first_missing_row): the enabled pairs whose
+        tuple is no key and the lowest such row, None when nothing is
+        missing."""
+        arity, n_tuples, table, values, sels = _lookup_tuple_lists(
+            self._width, value_tuples, table_columns, count_column, selectors)
+        ctx = context(device)
+        n, first = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().mlh_trace_lookup_tuple_counts(
+            ctx, ptr(self._matrix), self._height.bit_length() - 1, self._width, arity, table,
+            n_tuples, values, sels, count_column, ctypes.byref(n), ctypes.byref(first)), ctx)
+        return n.value, (None if first.value == 2 ** 64 - 1 else first.value)
+
+    def lookup_tuple_multiplicities(self, value_tuples, table_columns, count_column,
+                                    selectors=None, device=0):
+        """lookup_tuple_counts for a lookup that must hold: ValueError naming
+        the number of missing tuples and the first row with one."""
+        n, first = self.lookup_tuple_counts(value_tuples, table_columns, count_column, selectors,
+                                            device)
+        if n:
+            raise ValueError("%d looked-up tuple%s not in table columns %s, the first in row %d"
+                             % (n, "" if n == 1 else "s", tuple(table_columns), first))
+
+
+LOOKUP_MAX_ARITY, LOOKUP_MAX_TUPLES, LOOKUP_NO_SELECTOR = 8, 16, 0xFFFFFFFF
+
+
+def _lookup_tuple_lists(width, value_tuples, table_columns, count_column, selectors):
+    """The column lists of a tuple lookup, checked (ValueError), as the arrays
+    mlh_trace_lookup_tuple_counts takes: (arity, n_tuples, table, values,
+    selectors or None)."""
+    table = [int(c) for c in table_columns]
+    tuples = [[int(c) for c in t] for t in value_tuples]
+    arity, n_tuples = len(table), len(tuples)
+    if not 1 <= arity <= LOOKUP_MAX_ARITY:
+        raise ValueError("a tuple lookup has 1..%d table columns, not %d" % (LOOKUP_MAX_ARITY, arity))
+    if not 1 <= n_tuples <= LOOKUP_MAX_TUPLES:
+        raise ValueError("a tuple lookup has 1..%d value tuples, not %d"
+                         % (LOOKUP_MAX_TUPLES, n_tuples))
+    if arity * n_tuples > 32:
+        raise ValueError("%d tuples of arity %d are more than 32 value columns" % (n_tuples, arity))
+    if not 0 <= count_column < width:
+        raise ValueError("count column %r outside the trace" % (count_column,))
+    for c in table:
+        if not 0 <= c < width:
+            raise ValueError("table column %r outside the trace" % (c,))
+        if c == count_column:
+            raise ValueError("the count column %d is a table column" % c)
+    if len(set(table)) != arity:
+        raise ValueError("a table column occurs twice in %r" % (tuple(table),))
+    for t in tuples:
+        if len(t) != arity:
+            raise ValueError("value tuple %r has not the table's arity %d" % (tuple(t), arity))
+        for c in t:
+            if not 0 <= c < width:
+                raise ValueError("value column %r outside the trace" % (c,))
+            if c in table:
+                raise ValueError("the value column %d is a table column" % c)
+            if c == count_column:
+                raise ValueError("the count column %d is a value column" % c)
+    sels = None
+    if selectors is not None:
+        sels = [LOOKUP_NO_SELECTOR if s is None else int(s) for s in selectors]
+        if len(sels) != n_tuples:
+            raise ValueError("%d selectors for %d value tuples" % (len(sels), n_tuples))
+        for s in sels:
+            if s != LOOKUP_NO_SELECTOR and not 0 <= s < width:
+                raise ValueError("selector column %r outside the trace" % (s,))
+            if s == count_column:
+                raise ValueError("the count column %d is a selector" % s)
+        sels = (ctypes.c_uint32 * n_tuples)(*sels)
+    return (arity, n_tuples, (ctypes.c_uint32 * arity)(*table),
+            (ctypes.c_uint32 * (arity * n_tuples))(*[c for t in tuples for c in t]), sels)
+
+
+def lookup_tuple_counts_launch_info(log_height, n_tuples):
+    """(threads per block, blocks of the count launch, log2 of the slots)."""
+    t, b, s = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    check(lib().mlh_trace_lookup_tuple_counts_launch_info(log_height, n_tuples, ctypes.byref(t),
+                                                          ctypes.byref(b), ctypes.byref(s)))
+    return t.value, b.value, s.value
+
+
+def tuple_key(columns, alpha):
+    """var(c0) + alpha * (var(c1) + alpha * (...)): a tuple's components
+    compressed with ``alpha`` (an Expr such as ``rand(1)``, or an int), so that
+    a phase-2 fill and its constraint spell the key of a tuple lookup once."""
+    cols = [int(c) for c in columns]
+    if not cols:
+        raise ValueError("a tuple key needs a column")
+    alpha = Expr.wrap(alpha)
+    e = var(cols[-1])
+    for c in reversed(cols[:-1]):
+        e = var(c) + alpha * e
+    return e
 
 
 def _lookup_mask(width, value_columns, table_column, count_column):

@@ -1313,6 +1313,106 @@ mlh_status mlh_trace_lookup_counts_launch_info(uint32_t log_height, uint32_t n_v
   return MLH_OK;
 }
 
+// ---- the same for tuple keys ----
+
+static_assert(MLH_LOOKUP_MAX_ARITY == kLkMaxArity && MLH_LOOKUP_MAX_TUPLES == kLkMaxTuples &&
+                  MLH_LOOKUP_NO_SELECTOR == kLkNoSelector,
+              "mlhip.h and trace_lookup.hpp agree");
+
+// Checks the column lists and copies them into a (table columns) and lists.
+static bool lookup_tuple_columns_ok(uint32_t width, uint32_t arity, const uint32_t* table,
+                                    uint32_t n_tuples, const uint32_t* values,
+                                    const uint32_t* selectors, uint32_t C, LookupTupleArgs& a,
+                                    LookupTupleLists& lists) {
+  if (!table || !values || width < 1 || width > kCsMaxWidth || arity < 1 || arity > kLkMaxArity ||
+      n_tuples < 1 || n_tuples > kLkMaxTuples || arity * n_tuples > kLkMaxTupleColumns || C >= width)
+    return false;
+  uint32_t tmask = 0;
+  for (uint32_t c = 0; c < arity; ++c) {
+    if (table[c] >= width || table[c] == C || ((tmask >> table[c]) & 1u)) return false;
+    tmask |= 1u << table[c];
+    a.table_columns[c] = table[c];
+  }
+  for (uint32_t k = 0; k < arity * n_tuples; ++k) {
+    if (values[k] >= width || values[k] == C || ((tmask >> values[k]) & 1u)) return false;
+    lists.value_columns[k] = values[k];
+  }
+  for (uint32_t l = 0; l < n_tuples; ++l) {
+    const uint32_t s = selectors ? selectors[l] : kLkNoSelector;
+    if (s != kLkNoSelector && (s >= width || s == C)) return false;
+    lists.selector_columns[l] = s;
+  }
+  return true;
+}
+
+mlh_status mlh_trace_lookup_tuple_counts_shaped(mlh_ctx* ctx, void* dev_matrix,
+                                                uint32_t log_height, uint32_t width,
+                                                uint32_t arity, const uint32_t* table_columns,
+                                                uint32_t n_tuples, const uint32_t* value_columns,
+                                                const uint32_t* selector_columns,
+                                                uint32_t count_column, uint64_t* n_missing,
+                                                uint64_t* first_missing_row, uint32_t log_slots,
+                                                uint32_t hash_bits, uint32_t max_blocks,
+                                                uint32_t flags) {
+  LookupTupleArgs a{};
+  LookupTupleLists lists{};
+  if (!ctx || !dev_matrix || !n_missing || !first_missing_row || log_height > kLkMaxLogHeight ||
+      !lookup_tuple_columns_ok(width, arity, table_columns, n_tuples, value_columns,
+                               selector_columns, count_column, a, lists) ||
+      log_slots < log_height || log_slots > kLkMaxLogSlots || hash_bits > log_slots ||
+      (flags & ~kLkNoAggregate))
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_lookup_tuple_counts: bad argument");
+  PoolBuf scratch(ctx);  // the counters, the column lists and the slot array
+  MLH_TRY(scratch.alloc(lk_scratch_bytes(log_slots)));
+  a.m = reinterpret_cast<fe*>(dev_matrix);
+  a.log_height = log_height;
+  a.width = width;
+  a.arity = arity;
+  a.n_tuples = n_tuples;
+  a.count_column = count_column;
+  a.log_slots = log_slots;
+  a.hash_bits = hash_bits;
+  a.max_blocks = max_blocks;
+  a.flags = flags;
+  ProfScope ps(ctx, "trace_lookup_tuple_counts");
+  HIP_TRY(ctx, launch_lookup_tuple_insert(a, lists, scratch.p, ctx->stream));
+  HIP_TRY(ctx, launch_lookup_tuple_count(a, ctx->stream));
+  ps.end();
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, a.counters, sizeof(LookupCounters),
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  LookupCounters c;
+  memcpy(&c, ctx->pinned, sizeof(c));
+  *n_missing = c.n_missing;
+  *first_missing_row = c.first_missing_row == kLkEmpty ? UINT64_MAX : c.first_missing_row;
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_lookup_tuple_counts(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                         uint32_t width, uint32_t arity,
+                                         const uint32_t* table_columns, uint32_t n_tuples,
+                                         const uint32_t* value_columns,
+                                         const uint32_t* selector_columns, uint32_t count_column,
+                                         uint64_t* n_missing, uint64_t* first_missing_row) {
+  const uint32_t log_slots = lk_default_log_slots(log_height);
+  return mlh_trace_lookup_tuple_counts_shaped(ctx, dev_matrix, log_height, width, arity,
+                                              table_columns, n_tuples, value_columns,
+                                              selector_columns, count_column, n_missing,
+                                              first_missing_row, log_slots, log_slots, 0, 0);
+}
+
+mlh_status mlh_trace_lookup_tuple_counts_launch_info(uint32_t log_height, uint32_t n_tuples,
+                                                     uint32_t* threads, uint32_t* blocks,
+                                                     uint32_t* log_slots) {
+  if (!threads || !blocks || !log_slots || log_height > kLkMaxLogHeight || n_tuples < 1 ||
+      n_tuples > kLkMaxTuples)
+    return MLH_ERR_INVALID;
+  *threads = kLkThreads;
+  *blocks = lk_blocks((uint64_t)n_tuples << log_height, 0);
+  *log_slots = lk_default_log_slots(log_height);
+  return MLH_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
