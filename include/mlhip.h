@@ -274,7 +274,11 @@ mlh_status mlh_fri_proof_encode(const mlh_fri_proof* proof, uint8_t* out, uint64
 mlh_status mlh_fri_proof_decode_header(const uint8_t* in, uint64_t len, uint32_t* log_code,
                                        uint32_t* num_queries);
 mlh_status mlh_fri_proof_decode(const uint8_t* in, uint64_t len, mlh_fri_proof* proof);
-/* FriProof::verify (fri/mod.rs:287-340), host side; MLH_ERR_VERIFY if rejected. */
+/* FriProof::verify (fri/mod.rs:287-340), host side; MLH_ERR_VERIFY if rejected.
+ * Proof elements are canonical: last_elem or an opened leaf element that the
+ * verifier reads whose 16 bytes spell a value >= M is MLH_ERR_VERIFY.  The
+ * reference holds typed ReedSolomonPair<F> values (fri/mod.rs:177-236) and
+ * hashes their canonical bytes, so it cannot accept such a leaf. */
 mlh_status mlh_fri_verify(const mlh_fri_proof* proof);
 
 /* Batched open_query_at: nq records (layout above) for host indices idx[nq]. */
@@ -395,7 +399,9 @@ uint64_t mlh_batched_fri_query_bytes(uint32_t log_code, uint32_t num_codes);
 mlh_status mlh_batched_fri_prove(mlh_ctx* ctx, const void* dev_codes, uint32_t num_codes,
                                  uint32_t log_code, mlh_transcript* tr,
                                  mlh_batched_fri_proof* proof);
-/* BatchedFriProof::verify (batched_fri.rs:313-388), host side. */
+/* BatchedFriProof::verify (batched_fri.rs:313-388), host side.  last_elem or
+ * an opened element (batch column or inner leaf) >= M: MLH_ERR_VERIFY, as
+ * mlh_fri_verify (typed ReedSolomonPair<F>, fri/mod.rs:177-236). */
 mlh_status mlh_batched_fri_verify(const mlh_batched_fri_proof* proof);
 /* BatchedFriProverData step by step (batched_fri.rs:9-224), the transcript on
  * the host: what BatchedFriProverData::fold (:178-205) and BatchedPCSProverData
@@ -438,7 +444,10 @@ typedef struct mlh_batched_pcs_proof {
 mlh_status mlh_batched_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t num_polys,
                                  uint32_t n_vars, const uint8_t* inputs, const uint8_t* outputs,
                                  mlh_transcript* tr, mlh_batched_pcs_proof* proof);
-/* BatchedPCSProof::verify (batched_pcs.rs:182-250), host side. */
+/* BatchedPCSProof::verify (batched_pcs.rs:182-250), host side.  A sumcheck
+ * coefficient, last_elem or an opened element >= M: MLH_ERR_VERIFY, as
+ * mlh_fri_verify (typed ReedSolomonPair<F>, fri/mod.rs:177-236).  inputs and
+ * outputs are the caller's and are not range-checked here. */
 mlh_status mlh_batched_pcs_verify(const mlh_batched_pcs_proof* proof, uint32_t n_vars,
                                   const uint8_t* inputs, const uint8_t* outputs,
                                   mlh_transcript* tr);
@@ -1018,7 +1027,10 @@ typedef struct mlh_pcs_proof {
 mlh_status mlh_pcs_prove(mlh_ctx* ctx, const void* dev_evals, uint32_t n_vars,
                          const uint8_t* host_inputs, const uint8_t output[16], mlh_transcript* tr,
                          mlh_pcs_proof* proof);
-/* PCSProof::verify (multilinear_pcs.rs:138-190), host side. */
+/* PCSProof::verify (multilinear_pcs.rs:138-190), host side.  A sumcheck
+ * coefficient, last_elem or an opened leaf element >= M: MLH_ERR_VERIFY, as
+ * mlh_fri_verify (typed ReedSolomonPair<F>, fri/mod.rs:177-236).  host_inputs
+ * and output are the caller's and are not range-checked here. */
 mlh_status mlh_pcs_verify(const mlh_pcs_proof* proof, uint32_t n_vars, const uint8_t* host_inputs,
                           const uint8_t output[16], mlh_transcript* tr);
 

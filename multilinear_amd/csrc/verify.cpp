@@ -101,6 +101,16 @@ static bool verify_path(const uint8_t* value32, const uint8_t* sibs, uint32_t de
   return verify_path_len(value32, 32, sibs, depth, root, index);
 }
 
+// Proof elements are canonical: the reference's proofs hold typed field
+// elements (ReedSolomonPair<F>, fri/mod.rs:177-236) and hash their canonical
+// bytes, so 16 bytes that spell a value >= M cannot occur there.  Over raw
+// bytes that is a rejection (as cs_sumcheck_verify_rs's load_canonical).
+static bool all_canonical(const uint8_t* src, uint64_t n) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (h_load(src + 16 * i) >= kModulus) return false;
+  return true;
+}
+
 extern "C" {
 
 mlh_status mlh_merkle_verify(const uint8_t* value, uint64_t value_len, const uint8_t* sibs,
@@ -141,6 +151,7 @@ static bool query_chain(const uint8_t* rec, const uint8_t* commitments, uint32_t
     const uint32_t depth = depth0 - t;
     const uint8_t* val = rec + off;
     if (!verify_path(val, val + 32, depth, commitments + 32 * t, cur_idx)) return false;
+    if (!all_canonical(val, 2)) return false;
     const u128 v = h_load(val), mv = h_load(val + 16);
     const u128 gp = h_pow(cur_gen, cur_idx);
     const u128 even = h_mul(h_add(v, mv), inv2);
@@ -166,6 +177,7 @@ static mlh_status fri_verify_queries(const mlh_fri_proof* pf, mlh_transcript* tr
   const u128 gen = h_pow2_generator(L);
   const uint64_t qbytes = mlh_fri_query_bytes(L);
   const u128 last = h_load(pf->last_elem);
+  if (!all_canonical(pf->last_elem, 1)) return MLH_ERR_VERIFY;
   for (uint32_t q = 0; q < pf->num_queries; ++q) {
     uint64_t index;
     transcript_draw_indices(tr, domain / 2, 1, &index);
@@ -187,6 +199,7 @@ static mlh_status batched_verify_queries(const mlh_batched_fri_proof* pf, mlh_tr
   const u128 gen = h_pow2_generator(L);
   const uint64_t qbytes = mlh_batched_fri_query_bytes(L, m);
   const u128 inv2 = h_inv(2), last = h_load(pf->last_elem);
+  if (!all_canonical(pf->last_elem, 1)) return MLH_ERR_VERIFY;
   for (uint32_t q = 0; q < pf->num_queries; ++q) {
     uint64_t index;  // (drawn and absorbed; nothing below reads the transcript)
     transcript_draw_indices(tr, n, 1, &index);
@@ -194,6 +207,7 @@ static mlh_status batched_verify_queries(const mlh_batched_fri_proof* pf, mlh_tr
     const uint8_t* rec = pf->queries + q * qbytes;
     if (!verify_path_len(rec, 32ull * m, rec + 32ull * m, L - 1, pf->batch_commitment, index))
       return MLH_ERR_VERIFY;
+    if (!all_canonical(rec, 2ull * m)) return MLH_ERR_VERIFY;
     u128 v = 0, mv = 0;  // fingerprints (Horner over the codes)
     for (uint32_t j = 0; j < m; ++j) {
       v = h_add(h_mul(v, fr), h_load(rec + 32ull * j));
@@ -256,6 +270,7 @@ mlh_status mlh_pcs_verify(const mlh_pcs_proof* pf, uint32_t n_vars, const uint8_
   if (n_vars == 0 || !fri_header_ok(fp->log_code, fp->num_trees, n_vars) ||
       fp->log_code != n_vars + MLH_LOG_BLOWUP)
     return MLH_ERR_VERIFY;
+  if (!all_canonical(pf->sumcheck_polys, 2ull * n_vars)) return MLH_ERR_VERIFY;
   std::vector<u128> rs;
   for (uint32_t k = 0; k < n_vars; ++k) {
     mlh_transcript_absorb(tr, fp->commitments + 32 * k, 32);
@@ -325,6 +340,7 @@ mlh_status mlh_batched_pcs_verify(const mlh_batched_pcs_proof* pf, uint32_t n_va
   if (n_vars == 0 || fp->num_codes == 0 || !fri_header_ok(fp->log_code, fp->num_trees, n_vars - 1) ||
       fp->log_code != n_vars + MLH_LOG_BLOWUP)
     return MLH_ERR_VERIFY;
+  if (!all_canonical(pf->sumcheck_polys, 2ull * n_vars)) return MLH_ERR_VERIFY;
   const uint32_t m = fp->num_codes;
   for (uint32_t i = 0; i < n_vars; ++i) mlh_transcript_absorb(tr, inputs + 16 * i, 16);
   for (uint32_t j = 0; j < m; ++j) mlh_transcript_absorb(tr, outputs + 16 * j, 16);

@@ -124,6 +124,8 @@ class BatchedFriProof:
         log_domain = len(self.commitments) + 1 + LOG_BLOWUP
         domain = 1 << log_domain
         gen = F.pow_2_generator(log_domain)
+        if self.last_elem >= F.M:  # non-canonical proof element (oracle/fri.py verify_query)
+            return False
         for q in self.queries:
             n = domain // 2
             idx = query_index(tr, domain)
@@ -139,6 +141,8 @@ def verify_batched_query(q, proof, n, index, gen, rs, fr):  # batched_fri.rs:226
         return False
     if not MK.batch_verify(value, path, proof.batch_commitment, index):
         return False
+    if any(F.from_bytes(p[:16]) >= F.M or F.from_bytes(p[16:32]) >= F.M for p in value):
+        return False  # non-canonical proof element (oracle/fri.py verify_query)
     v = fingerprint(fr, [F.from_bytes(p[:16]) for p in value])
     mv = fingerprint(fr, [F.from_bytes(p[16:32]) for p in value])
     gp = F.fpow(gen, index)
@@ -209,6 +213,8 @@ class BatchedPCSProof:
             return False
         n = len(fp.commitments) + 1
         assert n == len(self.sumcheck_polynomials) == len(self.inputs)
+        if any(c >= F.M for poly in self.sumcheck_polynomials for c in poly):
+            return False  # non-canonical proof element (oracle/fri.py verify_query)
         for x in self.inputs:
             transcript.absorb(F.to_bytes(x))
         for y in self.outputs:

@@ -140,6 +140,8 @@ class FriProof:
         log_domain = len(self.commitments) + LOG_BLOWUP
         domain_size = 1 << log_domain
         gen = F.pow_2_generator(log_domain)
+        if self.last_elem >= F.M:  # a typed F cannot hold it (see verify_query)
+            return False
         for q in self.queries:
             n = domain_size // 2
             idx = query_index(tr, domain_size)
@@ -150,7 +152,10 @@ class FriProof:
 
 
 def verify_query(paths, commitments, last_element, n, index, gen, rs):
-    """QueryProof::verify (fri/mod.rs:184-236)."""
+    """QueryProof::verify (fri/mod.rs:184-236).  The reference's paths hold
+    typed ReedSolomonPair<F> values (fri/mod.rs:177-236) and hash their
+    canonical bytes, so a leaf whose 16-byte element is >= M cannot occur
+    there; over raw bytes that is an explicit rejection."""
     if len(paths) != len(commitments):
         return False
     cur_n, cur_idx, cur_gen = n, index, gen
@@ -159,6 +164,8 @@ def verify_query(paths, commitments, last_element, n, index, gen, rs):
             return False
         v = F.from_bytes(value[:16])
         mv = F.from_bytes(value[16:32])
+        if v >= F.M or mv >= F.M:
+            return False
         gp = F.fpow(cur_gen, cur_idx)
         even = F.div(v + mv, 2)
         odd = F.div(v - mv, F.mul(2, gp))

@@ -52,6 +52,8 @@ class PCSProof:
             return False
         n = len(fp.commitments)
         assert n == len(self.sumcheck_polynomials) == len(self.inputs)
+        if any(c >= F.M for poly in self.sumcheck_polynomials for c in poly):
+            return False  # non-canonical proof element (oracle/fri.py verify_query)
         rs = []
         for root, poly in zip(fp.commitments, self.sumcheck_polynomials):
             transcript.absorb(root)

@@ -81,14 +81,16 @@ def sumcheck(sysm, ot, sum_columns, beta, claim):
 
 
 def prove(seed, fns, degree, width, randoms, log_height, matrix, pre, sum_columns, total=None,
-          column_sum=None, matrix1=None):
+          column_sum=None, matrix1=None, matrix2=None):
     """-> dict: the proof's parts in host form and the transcript digests.
-    matrix1 (optional): the trace as commitment 1 saw it."""
+    matrix1 / matrix2 (optional): the trace as commitment 1 / 2 and its
+    opening saw it."""
     P, W = pre, width
     columns = S.columns_of(matrix, W)
     columns1 = S.columns_of(matrix if matrix1 is None else matrix1, W)[:P]
+    columns2 = S.columns_of(matrix if matrix2 is None else matrix2, W)[P:]
     root1 = S.batch_root(columns1, log_height)
-    root2 = S.batch_root(columns[P:], log_height) if P < W else None
+    root2 = S.batch_root(columns2, log_height) if P < W else None
     ot = OT.Transcript()
     ot.absorb(seed)
     entry = ot.random()
@@ -115,16 +117,18 @@ def prove(seed, fns, degree, width, randoms, log_height, matrix, pre, sum_column
     after_sumcheck = ot.random()
     coeff_bytes = b"".join(F.to_bytes(c) for p in pols for c in p)
     prefix += coeff_bytes
-    pcs1, prefix = S._open(ot, prefix, rs, output[:P], columns1, log_height)        # 7
+    openings = []
+    pcs1, prefix = S._open(ot, prefix, rs, output[:P], columns1, log_height, openings)  # 7
     pcs = [pcs1]
     if P < W:
-        pcs2, prefix = S._open(ot, prefix, rs, output[P:], columns[P:], log_height)  # 8
+        pcs2, prefix = S._open(ot, prefix, rs, output[P:], columns2, log_height, openings)  # 8
         pcs.append(pcs2)
         assert pcs2["batch_commitment"] == root2
     assert pcs1["batch_commitment"] == root1
     digest = ot.random()
     assert digest == pcs[-1]["last_random"]
-    return dict(seed=seed, entry=entry, root1=root1, root2=root2, sysm=sysm, matrix=matrix,
+    return dict(openings=openings,
+                seed=seed, entry=entry, root1=root1, root2=root2, sysm=sysm, matrix=matrix,
                 columns=columns, total=total, column_sum=column_sum, beta=beta, claim=claim,
                 trace_randoms=trace_randoms, before_sumcheck=before_sumcheck, pols=pols, rs=rs,
                 output=output, after_sumcheck=after_sumcheck, coeff_bytes=coeff_bytes, pcs=pcs,

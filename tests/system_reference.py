@@ -121,12 +121,15 @@ def _opening_bytes(tr, inputs, outputs, pcs):
     return b"".join(out)
 
 
-def _open(ot, prefix, rs, outputs, columns, log_height):
+def _open(ot, prefix, rs, outputs, columns, log_height, keep=None):
     """One BatchedPCSProof::prove on `ot` (advanced past it) -> (the proof's
-    parts, the prefix of whatever follows)."""
+    parts, the prefix of whatever follows).  keep (optional list): receives
+    the oracle's proof object where the Python batched PCS made it."""
     if log_height <= PY_MAX_LOG:
         before = ot.clone()
         pr = OB.BatchedPCSProof.prove(rs, outputs, columns, ot)
+        if keep is not None:
+            keep.append(pr)
         fp = pr.fri_proof
         pcs = dict(batch_commitment=fp.batch_commitment, commitments=list(fp.commitments),
                    polys=[tuple(p) for p in pr.sumcheck_polynomials], last_elem=fp.last_elem,
@@ -142,9 +145,11 @@ def _open(ot, prefix, rs, outputs, columns, log_height):
     return pcs, prefix + _opening_bytes(ot, rs, outputs, pcs)
 
 
-def prove(seed, fns, degree, width, randoms, log_height, matrix, total=None):
-    """-> dict: the proof's parts in host form and the transcript digests."""
-    columns = columns_of(matrix, width)
+def prove(seed, fns, degree, width, randoms, log_height, matrix, total=None, opening_matrix=None):
+    """-> dict: the proof's parts in host form and the transcript digests.
+    opening_matrix (optional): the trace the commitment and the opening see
+    (tests/forge_reference.py); sumcheck and output stay `matrix`'s."""
+    columns = columns_of(matrix if opening_matrix is None else opening_matrix, width)
     root = batch_root(columns, log_height)
     ot = OT.Transcript()
     ot.absorb(seed)
@@ -159,13 +164,14 @@ def prove(seed, fns, degree, width, randoms, log_height, matrix, total=None):
     output = tables.matrix[:width]
     after_sumcheck = ot.random()
     coeff_bytes = b"".join(F.to_bytes(c) for p in pols for c in p)
-    pcs, _ = _open(ot, seed + root + coeff_bytes, rs, output, columns, log_height)  # 4
+    openings = []
+    pcs, _ = _open(ot, seed + root + coeff_bytes, rs, output, columns, log_height, openings)  # 4
     digest = ot.random()
     assert pcs["batch_commitment"] == root
     return dict(seed=seed, entry=entry, root=root, sysm=sysm, matrix=matrix, columns=columns,
                 total=total, pols=pols, rs=rs, output=output, after_sumcheck=after_sumcheck,
                 coeff_bytes=coeff_bytes, pcs=pcs, digest=digest, log_height=log_height, width=width,
-                degree=degree)
+                degree=degree, openings=openings)
 
 
 CASES = {c.name: c for c in cs_cases.cases()}

@@ -14,6 +14,7 @@ from oracle import fri as OF
 from oracle import pcs as OP
 from oracle import polynomials as OPL
 from oracle import transcript as OT
+from test_verifier_forgeries_cpu import _fill_batched, _fill_fri_struct
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -151,31 +152,6 @@ def test_proof_sizes():
     assert lib.mlh_fri_query_bytes(L) == 32 * sum(1 + (L - 1 - t) for t in range(L - 1))
 
 
-def _fill_fri_struct(proof, log_code):
-    """Pack an oracle FriProof into the C struct layout of mlhip.h."""
-    from multilinear_amd import _lib as L
-
-    T = log_code - 1
-    commit = (ctypes.c_uint8 * (32 * T)).from_buffer_copy(b"".join(proof.commitments))
-    qb = L.load().mlh_fri_query_bytes(log_code)
-    raw = b""
-    for q in proof.queries:
-        for value, path in q:
-            raw += value + b"".join(s for s, _ in path)
-    assert len(raw) == qb * 128
-    qbuf = (ctypes.c_uint8 * len(raw)).from_buffer_copy(raw)
-    c = L.FriProofC()
-    c.log_code = log_code
-    c.num_trees = T
-    c.num_queries = 128
-    c.commitments = ctypes.cast(commit, ctypes.c_void_p)
-    c.last_elem[:] = list(F.to_bytes(proof.last_elem))
-    c.last_random[:] = list(proof.last_random)
-    c.query_indices = None
-    c.queries = ctypes.cast(qbuf, ctypes.c_void_p)
-    return c, (commit, qbuf)
-
-
 def test_host_fri_verifier_accepts_oracle_proof():
     """mlh_fri_verify (FriProof::verify, fri/mod.rs:287-340) on an oracle proof."""
     lib = _lib.load()
@@ -262,29 +238,6 @@ def test_fri_proof_wire_format_matches_oracle_encoding():
     bad[d_off] = 2
     with pytest.raises(_lib.MlhError):
         FriProof.from_bytes(bytes(bad))
-
-
-def _fill_batched(proof, log_code, m):
-    """oracle BatchedFriProof -> C layout (mlh_batched_fri_proof)."""
-    from multilinear_amd.batched import BatchedFriProof
-
-    p = BatchedFriProof(log_code, m)
-    raw = b""
-    for (col, bpath), inner in proof.queries:
-        raw += b"".join(col) + b"".join(s for s, _ in bpath)
-        for value, path in inner:
-            raw += value + b"".join(s for s, _ in path)
-    assert len(raw) == p.qbytes * 128
-    ctypes.memmove(p._q, raw, len(raw))
-    if proof.commitments:
-        ctypes.memmove(p._commit, b"".join(proof.commitments), 32 * len(proof.commitments))
-    p.c.num_trees = len(proof.commitments)
-    p.c.num_queries = 128
-    p.c.query_indices = None
-    p.c.batch_commitment[:] = list(proof.batch_commitment)
-    p.c.last_elem[:] = list(F.to_bytes(proof.last_elem))
-    p.c.last_random[:] = list(proof.last_random)
-    return p
 
 
 @pytest.mark.parametrize("m,log_n", [(1, 4), (3, 5), (2, 1)])
