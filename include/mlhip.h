@@ -806,6 +806,112 @@ mlh_status mlh_system_verify_phased(const mlh_cs_program* prog, uint32_t log_hei
                                     const uint8_t sum[16], const uint8_t column_sum[16],
                                     const mlh_phased_proof* proof, mlh_transcript* tr);
 
+/* ---- next-row constraints: shifted columns in the system proof -------------- *
+ * The rows are cyclic: next(c) at row i is column c of row (i + 1) mod
+ * 2^log_height.  A shifted system is a trace of width W, a list of K distinct
+ * source columns c_0 .. c_{K-1} (each < W, K >= 0, W + K <= 32) and an
+ * ordinary constraint program of width W' = W + K in which column W + k stands
+ * for next(c_k); the list travels beside the program, whose wire format is
+ * unchanged.  A constraint that should not hold across the wrap from the last
+ * row to row 0 is gated by a selector column of the caller's, e.g.
+ * (1 - last) * (next(a) - a - b).  The sumcheck folds rows pairwise, so "the
+ * next row" is a protocol step and no addressing mode.  Transcript order, on
+ * top of the two-phase proof's:
+ *   1-5. as mlh_system_prove_phased (the program's randoms and constraints);
+ *   6. the constraint sumcheck (mlh_cs_sumcheck_prove_sums) on the extension E,
+ *      2^log_height x W': E[i][j] = T[i][j], j < W, E[i][W + k] =
+ *      T[(i + 1) mod 2^log_height][c_k]; the sum-column mask names real
+ *      columns only; output = row 0 of the folded E: T_j(rs) for j < W and
+ *      N_k = sum_i eq(rs, i) T_{c_k}(i + 1) for the rest;
+ *   7. only if K > 0: absorb the W' elements of output (16 W' bytes, in
+ *      order), lambda = next_challenge(), then mlh_cs_sumcheck_prove of
+ *        sum_j succ_rs[j] sum_k lambda^k T_{c_k}[j] = sum_k lambda^k N_k
+ *      on an untouched copy of T, with delta succ_rs[j] = eq_rs[(j - 1) mod
+ *      2^log_height] (mlh_eq_table of rs rotated by one row), the one
+ *      constraint sum_k rand(k) var(c_k) of declared degree 1 (two
+ *      coefficients per round), randoms lambda^0 .. lambda^(K-1) and mask [1]:
+ *      shift_polys, the point rs' and output2 = T_j(rs'), j < W.  The
+ *      verifier's final check is
+ *        succ(rs, rs') sum_k lambda^k output2[c_k] = pol_last(r_last)
+ *      with succ in closed form (mlh_shift_succ_evaluate);
+ *   8. BatchedPCSProof::prove on commitment 1 at (rs, output[0:P]), if P < W
+ *      on commitment 2 at (rs, output[P:W]); then, only if K > 0, on the same
+ *      commitments in the same order at (rs', output2[0:P]) and (rs',
+ *      output2[P:W]).  Both commitments are opened at rs' whether or not they
+ *      hold a source column: one rule, no evaluation in the proof unbound.
+ * With K = 0 the proof bytes and the final transcript state are
+ * mlh_system_prove_phased's. */
+/* dev_out (row-major 2^log_height x (width + n_shifts)) = the extension E of
+ * the row-major 2^log_height x width dev_matrix, which is not modified.  Out of
+ * place; width >= 1, width + n_shifts <= 32, log_height 0..32 (one row is its
+ * own next row); MLH_ERR_INVALID for a null pointer, a source column at or above
+ * width, overlapping buffers.  Duplicates are allowed here (the proof's list
+ * must be distinct).  One kernel launch on the context stream. */
+mlh_status mlh_trace_extend_next(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                 uint32_t width, const uint32_t* shift_columns, uint32_t n_shifts,
+                                 void* dev_out);
+/* Its launch shape: the rows of E a block writes per tile and the number of
+ * blocks; a block visits ceil(tiles / blocks) tiles of tile_rows rows and
+ * reads tile_rows + 1 rows of the trace for each. */
+mlh_status mlh_trace_extend_next_launch_info(uint32_t log_height, uint32_t width, uint32_t n_shifts,
+                                             uint32_t* tile_rows, uint32_t* blocks);
+/* dev_out[j] = dev_in[(j - 1) mod 2^log_n], 2^log_n elements, out of place
+ * (log_n 0..32): mlh_eq_table(x) -> the table of y -> succ(x, y). */
+mlh_status mlh_eq_table_rotate(mlh_ctx* ctx, const void* dev_in, uint32_t log_n, void* dev_out);
+/* succ(x, y) = sum_i eq(x, i) eq(y, (i + 1) mod 2^n) in O(n) field operations,
+ * host only; x, y: n canonical elements each (n 0..64; n = 0 gives 1).  With
+ * x_b the coordinate of bit b of the row index, bit b <-> point[n - 1 - b]
+ * (Mask::evaluate's order, evaluation.rs:56-73):
+ *   succ(x, y) = sum_{k<n} prod_{b<k} x_b (1 - y_b) * (1 - x_k) y_k
+ *                * prod_{b>k} (x_b y_b + (1 - x_b)(1 - y_b))  +  prod_b x_b (1 - y_b)
+ * (the carry of i + 1 stops at bit k; the last term is the wrap 2^n - 1 -> 0).
+ * MLH_ERR_INVALID for a null pointer or a non-canonical element. */
+mlh_status mlh_shift_succ_evaluate(const uint8_t* x, const uint8_t* y, uint32_t n, uint8_t out[16]);
+typedef struct mlh_shifted_proof {
+  uint32_t log_height, width /* W */, degree;
+  uint32_t pre_random_columns; /* P */
+  uint32_t sum_column_mask;    /* S, bit j = column j < W */
+  uint32_t n_shifts;           /* K */
+  uint32_t shift_columns[32];  /* c_0 .. c_{K-1}; the rest zero */
+  uint8_t* sumcheck_polys;     /* [log_height][degree+1][16]                     */
+  uint8_t* output;             /* [W + K][16]: row 0 of the folded extension     */
+  uint8_t* shift_polys;        /* [log_height][2][16]; unused when K = 0         */
+  uint8_t* output2;            /* [W][16] = Trace::evaluate(rs'); unused, K = 0  */
+  /* caller-allocated as for mlh_phased_proof: pcs at rs, pcs_shift at rs'
+   * (unused when K = 0); [1] unused when P = W */
+  mlh_batched_pcs_proof pcs[2];
+  mlh_batched_pcs_proof pcs_shift[2];
+} mlh_shifted_proof;
+/* The prover, steps 1-8.  prog: the W'-wide program; commitment1 / 2 as for
+ * mlh_system_prove_phased over the W real columns (W = their widths' sum).
+ * dev_matrix, the 2^log_height x W trace, is NOT modified: the extension, the
+ * copy of step 7 and the two delta tables come from the context pool, where
+ * they return on every path once the stream is drained (peak: (2 W + K + 2)
+ * 2^log_height elements beside the handles).  Nothing is committed or encoded
+ * a second time.  MLH_ERR_INVALID for a duplicate or out-of-range source column,
+ * W + K other than the program's width or above 32, a sum-mask bit at or above
+ * W, K > 0 with shift_columns, proof->shift_polys or proof->output2 null, and
+ * every argument error of the phased call.  On any non-OK return the
+ * transcript is exactly as at entry.  A trace that breaks a constraint is not
+ * detected here: MLH_OK, and the verifier rejects. */
+mlh_status mlh_system_prove_shifted(mlh_ctx* ctx, const mlh_cs_program* prog,
+                                    const mlh_trace_commitment* commitment1,
+                                    const mlh_trace_commitment* commitment2,
+                                    uint32_t sum_column_mask, const uint32_t* shift_columns,
+                                    uint32_t n_shifts, const void* dev_matrix,
+                                    const uint8_t sum[16], const uint8_t column_sum[16],
+                                    mlh_transcript* tr, mlh_shifted_proof* proof);
+/* The verifier, host only, in the same order.  MLH_ERR_INVALID for a null
+ * pointer or a shift list the prover would refuse; MLH_ERR_VERIFY, with the
+ * transcript exactly as at entry, for any rejection, any disagreement between
+ * the proof's header or shift list and the arguments, and any non-canonical
+ * element.  On MLH_OK the transcript ends in the prover's state. */
+mlh_status mlh_system_verify_shifted(const mlh_cs_program* prog, uint32_t log_height,
+                                     uint32_t pre_random_columns, uint32_t sum_column_mask,
+                                     const uint32_t* shift_columns, uint32_t n_shifts,
+                                     const uint8_t sum[16], const uint8_t column_sum[16],
+                                     const mlh_shifted_proof* proof, mlh_transcript* tr);
+
 /* ---- phase 2 on the device: fill programs and the column sum --------------- *
  * Between mlh_system_trace_randoms and mlh_trace_commit_range of the columns
  * at and above P the prover fills "the columns that you must fill" after

@@ -97,6 +97,24 @@ class PhasedProofC(ctypes.Structure):
     ]
 
 
+class ShiftedProofC(ctypes.Structure):
+    _fields_ = [
+        ("log_height", ctypes.c_uint32),
+        ("width", ctypes.c_uint32),
+        ("degree", ctypes.c_uint32),
+        ("pre_random_columns", ctypes.c_uint32),
+        ("sum_column_mask", ctypes.c_uint32),
+        ("n_shifts", ctypes.c_uint32),
+        ("shift_columns", ctypes.c_uint32 * 32),
+        ("sumcheck_polys", ctypes.c_void_p),
+        ("output", ctypes.c_void_p),
+        ("shift_polys", ctypes.c_void_p),
+        ("output2", ctypes.c_void_p),
+        ("pcs", BatchedPcsProofC * 2),
+        ("pcs_shift", BatchedPcsProofC * 2),
+    ]
+
+
 # mlh_transport (include/mlhip.h): collectives as C callbacks
 ALL_TO_ALL_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_uint64, ctypes.c_void_p)
@@ -253,6 +271,15 @@ SIGNATURES = {
     "mlh_system_prove_phased": (_I, [_P, _P, _P, _P, _U32, _P, _P, _P, _P,
                                      ctypes.POINTER(PhasedProofC)]),
     "mlh_system_verify_phased": (_I, [_P, _U32, _U32, _U32, _P, _P, ctypes.POINTER(PhasedProofC), _P]),
+    "mlh_trace_extend_next": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(_U32), _U32, _P]),
+    "mlh_trace_extend_next_launch_info": (_I, [_U32, _U32, _U32, ctypes.POINTER(_U32),
+                                               ctypes.POINTER(_U32)]),
+    "mlh_eq_table_rotate": (_I, [_P, _P, _U32, _P]),
+    "mlh_shift_succ_evaluate": (_I, [_P, _P, _U32, _P]),
+    "mlh_system_prove_shifted": (_I, [_P, _P, _P, _P, _U32, ctypes.POINTER(_U32), _U32, _P, _P, _P,
+                                      _P, ctypes.POINTER(ShiftedProofC)]),
+    "mlh_system_verify_shifted": (_I, [_P, _U32, _U32, _U32, ctypes.POINTER(_U32), _U32, _P, _P,
+                                       ctypes.POINTER(ShiftedProofC), _P]),
     "mlh_fill_program_create": (_I, [_P, _U64, ctypes.POINTER(_P)]),
     "mlh_fill_program_destroy": (None, [_P]),
     "mlh_fill_program_width": (_U32, [_P]),

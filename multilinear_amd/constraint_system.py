@@ -18,7 +18,10 @@ columns and hands out the trace randoms, the caller fills the other columns
 ``inv``, run in place by mlh_trace_fill; or ``field_inv`` and the other field
 ops below on column vectors), and ``prove`` / ``PhasedSystemProof.verify`` are
 mlh_system_prove_phased / _verify_phased, the column sum by default from
-mlh_trace_column_sum.  A lookup's multiplicity column, which is pre-random, is
+mlh_trace_column_sum.  A constraint set may refer to the next row with
+``nxt(j)`` (a shifted system: ``compile_shifted``, ``Trace.extend_next``);
+``PhasedProver.prove`` then runs mlh_system_prove_shifted and returns a
+``ShiftedSystemProof``.  A lookup's multiplicity column, which is pre-random, is
 counted in place before ``phased_prover`` by ``Trace.lookup_multiplicities``
 (mlh_trace_lookup_counts), or, for keys of several columns such as (x, y, x ^ y),
 by ``Trace.lookup_tuple_multiplicities`` (mlh_trace_lookup_tuple_counts);
@@ -100,6 +103,12 @@ def inv(e):
     return Expr("inv", Expr.wrap(e))
 
 
+def nxt(j):
+    """Column j of the next row, (i + 1) mod height at row i: a shifted column
+    of a shifted system (compile_shifted; include/mlhip.h)."""
+    return Expr("nxt", int(j))
+
+
 # ---- wire format -------------------------------------------------------------
 
 def encode_program(width, n_randoms, consts, n_temps, instrs, outs, degree):
@@ -131,7 +140,7 @@ def _emit_outputs(exprs, allow_inv):
     def need(e):  # temps needed to evaluate e (Sethi-Ullman)
         k = id(e)
         if k not in need_memo:
-            if e.op in ("var", "rand", "const"):
+            if e.op in ("var", "rand", "const", "nxt"):
                 need_memo[k] = 0
             elif e.op in _UNARY:
                 need_memo[k] = max(1, need(e.args[0]))
@@ -165,6 +174,8 @@ def _emit_outputs(exprs, allow_inv):
             return (COL, e.args[0])
         if e.op == "rand":
             return (RAND, e.args[0])
+        if e.op == "nxt":
+            raise ValueError("nxt() needs a shifted system (compile_shifted)")
         if e.op == "const":
             if e.args[0] not in consts:
                 consts.append(e.args[0])
@@ -204,6 +215,37 @@ def compile_program(exprs, width, n_randoms, degree):
     ValueError for an ``inv`` node."""
     consts, n_temps, instrs, outs = _emit_outputs(exprs, allow_inv=False)
     return encode_program(width, n_randoms, consts, n_temps, instrs, outs, degree)
+
+
+def compile_shifted(exprs, width, n_randoms, degree):
+    """Expressions with ``nxt`` -> (wire bytes, shift list): the distinct
+    ``nxt`` columns in order of first appearance become columns width, width +
+    1, ... of an ordinary program of width ``width + len(shift list)``, the
+    program mlh_system_prove_shifted takes beside the list.  Without ``nxt``
+    the bytes are compile_program's and the list is empty."""
+    shifts, memo = [], {}
+
+    def rewrite(e):
+        k = id(e)
+        if k not in memo:
+            if e.op == "nxt":
+                c = e.args[0]
+                if not 0 <= c < width:
+                    raise ValueError("nxt(%r): column outside the trace" % (c,))
+                if c not in shifts:
+                    shifts.append(c)
+                memo[k] = var(width + shifts.index(c))
+            elif e.op in ("var", "rand", "const"):
+                memo[k] = e
+            else:
+                memo[k] = Expr(e.op, *[rewrite(a) for a in e.args])
+        return memo[k]
+
+    exprs = [Expr.wrap(e) for e in exprs]  # (kept alive: the memo is keyed by id)
+    out = [rewrite(e) for e in exprs]
+    if width + len(shifts) > 32:
+        raise ValueError("%d columns and %d shifted ones are more than 32" % (width, len(shifts)))
+    return compile_program(out, width + len(shifts), n_randoms, degree), shifts
 
 
 def compile_fill(assignments, width, n_randoms):
@@ -373,6 +415,20 @@ class Trace:
         check(lib().mlh_trace_fill(ctx, prog.h, ptr(self._matrix), self._height.bit_length() - 1,
                                    self._width, _elems(randoms)), ctx)
         return prog
+
+    def extend_next(self, shift_columns, device=0):
+        """The extension of a shifted system (mlh_trace_extend_next): a new
+        Trace of width + len(shift_columns) columns whose column width + k is
+        column shift_columns[k] of the next row, cyclically; this trace is not
+        modified."""
+        cols = [int(c) for c in shift_columns]
+        K, L = len(cols), self._height.bit_length() - 1
+        ctx = context(device)
+        out = empty(self._height * (self._width + K), device)
+        arr = (ctypes.c_uint32 * max(K, 1))(*cols)
+        check(lib().mlh_trace_extend_next(ctx, ptr(self._matrix), L, self._width, arr, K, ptr(out)),
+              ctx)
+        return Trace(out, self._width + K)
 
     def lookup_counts(self, value_columns, table_column, count_column, device=0):
         """A lookup's multiplicities, in place (mlh_trace_lookup_counts): column
@@ -656,6 +712,13 @@ def _program_of(constraints, layout):
                                    constraints.degree()))
 
 
+def _shifted_program_of(constraints, layout):
+    """-> (Program, shift list): compile_shifted of the constraint set."""
+    wire, shifts = compile_shifted(constraints.constraints(), layout.columns, layout.randoms,
+                                   constraints.degree())
+    return Program(wire), shifts
+
+
 class _ProofHolder:
     """What SystemProof and PhasedSystemProof share: the header, the buffers of
     the sumcheck polynomials and of Trace::evaluate(rs) behind the C struct
@@ -752,6 +815,69 @@ class PhasedSystemProof(_ProofHolder):
                                               transcript.h) == 0
 
 
+class ShiftedSystemProof(_ProofHolder):
+    """mlh_shifted_proof: the phased proof over the extended trace (output has
+    width + K elements), the shift reduction's polynomials, Trace::evaluate(rs')
+    and the openings of both commitments at rs and at rs'."""
+
+    def __init__(self, log_height, width, degree, pre_random_columns, sum_column_mask,
+                 shift_columns):
+        super().__init__(_lib.ShiftedProofC(), log_height, width, degree)
+        self.pre_random_columns, self.sum_column_mask = pre_random_columns, sum_column_mask
+        self.shift_columns = [int(c) for c in shift_columns]
+        K, P, c = len(self.shift_columns), pre_random_columns, self.c
+        self._output = (ctypes.c_uint8 * (16 * (width + K)))()
+        self._shift_polys = (ctypes.c_uint8 * (32 * log_height))()
+        self._output2 = (ctypes.c_uint8 * (16 * width))()
+        c.output = ctypes.cast(self._output, ctypes.c_void_p)
+        c.shift_polys = ctypes.cast(self._shift_polys, ctypes.c_void_p)
+        c.output2 = ctypes.cast(self._output2, ctypes.c_void_p)
+        c.pre_random_columns, c.sum_column_mask, c.n_shifts = P, sum_column_mask, K
+        for k, col in enumerate(self.shift_columns):
+            c.shift_columns[k] = col
+        widths = [P] + ([width - P] if P < width else [])
+        self.pcs = [BatchedPCSProof(log_height, w) for w in widths]
+        self.pcs_shift = [BatchedPCSProof(log_height, w) for w in widths] if K else []
+        for i, p in enumerate(self.pcs):
+            c.pcs[i] = p.c
+        for i, p in enumerate(self.pcs_shift):
+            c.pcs_shift[i] = p.c
+
+    def _nested(self):
+        return ([(p, self.c.pcs[i]) for i, p in enumerate(self.pcs)]
+                + [(p, self.c.pcs_shift[i]) for i, p in enumerate(self.pcs_shift)])
+
+    @property
+    def commitments(self):
+        return [bytes(self.c.pcs[i].fri.batch_commitment) for i in range(len(self.pcs))]
+
+    @property
+    def output(self):
+        return _split(self._output, self.width + len(self.shift_columns))
+
+    @property
+    def shift_polynomials(self):
+        if not self.shift_columns:
+            return []
+        flat = _split(self._shift_polys, 2 * self.log_height)
+        return [flat[2 * k:2 * k + 2] for k in range(self.log_height)]
+
+    @property
+    def output2(self):
+        return _split(self._output2, self.width) if self.shift_columns else []
+
+    def verify(self, transcript, constraints, layout, total_sum, column_sum):
+        """mlh_system_verify_shifted, host only: True iff accepted.  The
+        constraint set is the prover's, with its ``nxt`` columns; the transcript
+        is the one the prover started from and is advanced only on True."""
+        prog, shifts = _shifted_program_of(constraints, layout)
+        arr = (ctypes.c_uint32 * max(len(shifts), 1))(*shifts)
+        return lib().mlh_system_verify_shifted(prog.h, self.log_height, layout.pre_random_columns,
+                                               _column_mask(layout), arr, len(shifts),
+                                               fe_bytes(total_sum), fe_bytes(column_sum),
+                                               ctypes.byref(self.c), transcript.h) == 0
+
+
 class PhasedProver:
     """System::prover for a layout with pre_random_columns / sum_columns
     (system.rs:17-30, 56-72): holds the commitment to columns [0, P) and the
@@ -764,7 +890,7 @@ class PhasedProver:
             raise ValueError("pre_random_columns must be in 1..columns, columns the trace's width")
         self._constraints, self._layout, self._trace, self._device = constraints, layout, trace, device
         self._mask = _column_mask(layout)
-        self.program = _program_of(constraints, layout)
+        self.program, self.shift_columns = _shifted_program_of(constraints, layout)
         self._com1 = Commitment.new(trace, device, columns=(0, P))
         out = (ctypes.c_uint8 * (16 * max(layout.randoms, 1)))()
         check(lib().mlh_system_trace_randoms(transcript.h, self._com1.root(), layout.randoms, out))
@@ -799,6 +925,18 @@ class PhasedProver:
             column_sum = trace_column_sum(t.matrix(), W, lay.sum_columns, self._device)
         self.column_sum = column_sum
         com2 = Commitment.new(t, self._device, columns=(P, W - P)) if P < W else None
+        if self.shift_columns:  # a shifted constraint set: the trace itself is not modified
+            K = len(self.shift_columns)
+            p = ShiftedSystemProof(self._com1.log_height, W, self._constraints.degree(), P,
+                                   self._mask, self.shift_columns)
+            check(lib().mlh_system_prove_shifted(ctx, self.program.h, self._com1.h,
+                                                 com2.h if com2 else None, self._mask,
+                                                 (ctypes.c_uint32 * K)(*self.shift_columns), K,
+                                                 ptr(t.matrix()), fe_bytes(total_sum),
+                                                 fe_bytes(column_sum), transcript.h,
+                                                 ctypes.byref(p.c)), ctx)
+            p._sync()
+            return p
         p = PhasedSystemProof(self._com1.log_height, W, self._constraints.degree(), P, self._mask)
         work = t.matrix().clone()
         check(lib().mlh_system_prove_phased(ctx, self.program.h, self._com1.h,

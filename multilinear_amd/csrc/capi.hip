@@ -49,6 +49,7 @@
 #include "trace_commit.hpp"
 #include "trace_fill.hpp"
 #include "trace_lookup.hpp"
+#include "trace_shift.hpp"
 #include "transcript_dev.hpp"
 
 using namespace mlh;
@@ -1592,19 +1593,46 @@ mlh_status mlh_cs_sumcheck_prove_sums(mlh_ctx* ctx, const mlh_cs_program* prog, 
 // ChallengeSet -> constraint sumcheck -> batched PCS opening of the committed
 // columns at the sumcheck's point.
 // ---------------------------------------------------------------------------
-// What follows the argument checks of both system provers: the transcript
+// Drains the stream when it leaves scope (null: nothing): declared behind the
+// pooled buffers of a call, it runs before they go back to the pool, on every
+// return path.
+struct StreamDrain {
+  mlh_ctx* ctx;
+  explicit StreamDrain(mlh_ctx* c) : ctx(c) {}
+  ~StreamDrain() {
+    if (ctx) (void)hipStreamSynchronize(ctx->stream);
+  }
+};
+// The shift part of mlh_system_prove_shifted as the prover core sees it.
+struct ShiftProve {
+  const uint32_t* cols;
+  uint32_t K;
+  void* dev_copy;  // the W-wide trace, untouched; folded here
+  void* dev_succ;  // 2^L elements of scratch: the rotated eq table
+  uint8_t* polys_out;
+  uint8_t* output2_out;
+  mlh_batched_pcs_proof* pcs1;
+  mlh_batched_pcs_proof* pcs2;
+};
+// What follows the argument checks of the system provers: the transcript
 // head, delta = eq(row), the sumcheck rounds, output = row 0 of the folded
 // matrix, then BatchedPCSProof::prove(inputs = rs, outputs = output) on each
 // handle's codes, evaluations and batch tree -- com1 for its columns into pcs1,
 // com2 (null: one phase) for the rest into pcs2.  A failure leaves the
 // transcript as at entry, the root absorbed first included.
+// sh (null: none; K = 0: none, but the stream is drained before the pooled
+// delta table goes back): dev_matrix is then the extension, prog->p.width = W
+// + K columns wide, and after the sumcheck comes the shift reduction on
+// sh->dev_copy (mlhip.h, step 7) and, behind the openings at rs, those of the
+// same handles at rs'.
 static mlh_status system_prove_core(mlh_ctx* ctx, const mlh_cs_program* prog,
                                     const mlh_trace_commitment* com1,
                                     const mlh_trace_commitment* com2, uint32_t sum_column_mask,
                                     void* dev_matrix, const uint8_t sum[16],
                                     const uint8_t* column_sum, mlh_transcript* tr,
                                     uint8_t* polys_out, uint8_t* output_out,
-                                    mlh_batched_pcs_proof* pcs1, mlh_batched_pcs_proof* pcs2) {
+                                    mlh_batched_pcs_proof* pcs1, mlh_batched_pcs_proof* pcs2,
+                                    const ShiftProve* sh = nullptr) {
   const uint32_t L = com1->log_height, W = prog->p.width;
   TranscriptGuard guard(tr);
   SystemHead h(prog->p, L);
@@ -1612,6 +1640,8 @@ static mlh_status system_prove_core(mlh_ctx* ctx, const mlh_cs_program* prog,
                   column_sum, &h) != MLH_OK)
     return fail(ctx, MLH_ERR_INVALID, "challenge set");
   PoolBuf delta(ctx);
+  StreamDrain drain(sh ? ctx : nullptr);
+  if (sh && !sh->K) sh = nullptr;  // no shifted column: the phased proof from here on
   MLH_TRY(delta.alloc(16ull << L));
   MLH_TRY(mlh_eq_table(ctx, h.row.data(), L, delta.p));
   std::vector<uint8_t> rs(16ull * L);
@@ -1625,6 +1655,28 @@ static mlh_status system_prove_core(mlh_ctx* ctx, const mlh_cs_program* prog,
   HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev_matrix, 16ull * W, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   std::vector<uint8_t> output(ctx->pinned, ctx->pinned + 16ull * W);
+  std::vector<uint8_t> rs2(16ull * L), output2;
+  if (sh) {  // step 7: sum_j succ_rs[j] sum_k lambda^k T_{c_k}[j] = sum_k lambda^k N_k
+    ProfScope ps(ctx, "system_shift_sumcheck");
+    const uint32_t Wt = W - sh->K;
+    mlh_cs_program sp;
+    if (!cs_shift_program(Wt, sh->cols, sh->K, sp.p)) return fail(ctx, MLH_ERR_INVALID, "shift list");
+    std::vector<uint8_t> lambdas;
+    uint8_t claim2[16], one[16];
+    h_store(one, 1);
+    shift_challenge(tr, output.data(), Wt, sh->K, &lambdas, claim2);
+    // eq(rs) into the delta table the sumcheck has consumed, rotated by a row
+    MLH_TRY(mlh_eq_table(ctx, rs.data(), L, delta.p));
+    HIP_TRY(ctx, launch_eq_rotate(delta.as<const fe>(), reinterpret_cast<fe*>(sh->dev_succ), L,
+                                  ctx->stream));
+    MLH_TRY(mlh_cs_sumcheck_prove(ctx, &sp, Wt, sh->dev_copy, sh->dev_succ, L, lambdas.data(), one,
+                                  claim2, tr, sh->polys_out, rs2.data()));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, sh->dev_copy, 16ull * Wt, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    output2.assign(ctx->pinned, ctx->pinned + 16ull * Wt);
+    ps.end();
+  }
   {
     ProfScope ps(ctx, "system_open");
     MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com1->codes), com1->evals,
@@ -1638,6 +1690,18 @@ static mlh_status system_prove_core(mlh_ctx* ctx, const mlh_cs_program* prog,
                              reinterpret_cast<const uint8_t*>(com2->tree), com2->width, L, rs.data(),
                              output.data() + 16ull * com1->width, tr, pcs2));
     ps.end();
+  }
+  if (sh) {  // the same handles at (rs', output2)
+    ProfScope ps(ctx, "system_open_shift");
+    MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com1->codes), com1->evals,
+                             reinterpret_cast<const uint8_t*>(com1->tree), com1->width, L, rs2.data(),
+                             output2.data(), tr, sh->pcs1));
+    if (com2)
+      MLH_TRY(batched_pcs_open(ctx, reinterpret_cast<const fe*>(com2->codes), com2->evals,
+                               reinterpret_cast<const uint8_t*>(com2->tree), com2->width, L,
+                               rs2.data(), output2.data() + 16ull * com1->width, tr, sh->pcs2));
+    ps.end();
+    memcpy(sh->output2_out, output2.data(), output2.size());
   }
   memcpy(output_out, output.data(), output.size());
   guard.keep();
@@ -1693,6 +1757,106 @@ mlh_status mlh_system_prove_phased(mlh_ctx* ctx, const mlh_cs_program* prog,
   proof->degree = prog->p.degree;
   proof->pre_random_columns = P1;
   proof->sum_column_mask = sum_column_mask;
+  return MLH_OK;
+}
+
+// ---- shifted columns (trace_shift.hip; mlhip.h gives the protocol) -------------
+mlh_status mlh_trace_extend_next(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
+                                 uint32_t width, const uint32_t* shift_columns, uint32_t n_shifts,
+                                 void* dev_out) {
+  if (!ctx || !dev_matrix || !dev_out || (n_shifts && !shift_columns))
+    return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (width < 1 || n_shifts > kTsMaxWidth || width + n_shifts > kTsMaxWidth ||
+      log_height > kCsMaxLogHeight)
+    return fail(ctx, MLH_ERR_INVALID, "width + n_shifts 1..32, log_height 0..32");
+  for (uint32_t k = 0; k < n_shifts; ++k)
+    if (shift_columns[k] >= width) return fail(ctx, MLH_ERR_INVALID, "source column outside the trace");
+  const uint64_t in_bytes = (16ull * width) << log_height;
+  const uint64_t out_bytes = (16ull * (width + n_shifts)) << log_height;
+  if (ranges_overlap(dev_matrix, dev_out, (uintptr_t)dev_matrix < (uintptr_t)dev_out ? in_bytes : out_bytes))
+    return fail(ctx, MLH_ERR_INVALID, "the extension is out of place: the buffers overlap");
+  ProfScope ps(ctx, "trace_extend_next");
+  HIP_TRY(ctx, launch_trace_extend_next(reinterpret_cast<const fe*>(dev_matrix),
+                                        reinterpret_cast<fe*>(dev_out), log_height, width,
+                                        shift_columns, n_shifts, ctx->stream));
+  ps.end();
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_extend_next_launch_info(uint32_t log_height, uint32_t width, uint32_t n_shifts,
+                                             uint32_t* tile_rows, uint32_t* blocks) {
+  if (!tile_rows || !blocks || width < 1 || n_shifts > kTsMaxWidth ||
+      width + n_shifts > kTsMaxWidth || log_height > kCsMaxLogHeight)
+    return MLH_ERR_INVALID;
+  *tile_rows = 1u << ts_log_rows(log_height, width + n_shifts);
+  *blocks = ts_blocks(log_height, width + n_shifts);
+  return MLH_OK;
+}
+
+mlh_status mlh_eq_table_rotate(mlh_ctx* ctx, const void* dev_in, uint32_t log_n, void* dev_out) {
+  if (!ctx || !dev_in || !dev_out || log_n > 32) return fail(ctx, MLH_ERR_INVALID, "bad argument");
+  if (ranges_overlap(dev_in, dev_out, 16ull << log_n))
+    return fail(ctx, MLH_ERR_INVALID, "the rotation is out of place: the buffers overlap");
+  ProfScope ps(ctx, "eq_rotate");
+  HIP_TRY(ctx, launch_eq_rotate(reinterpret_cast<const fe*>(dev_in), reinterpret_cast<fe*>(dev_out),
+                                log_n, ctx->stream));
+  ps.end();
+  return MLH_OK;
+}
+
+mlh_status mlh_system_prove_shifted(mlh_ctx* ctx, const mlh_cs_program* prog,
+                                    const mlh_trace_commitment* com1,
+                                    const mlh_trace_commitment* com2, uint32_t sum_column_mask,
+                                    const uint32_t* shift_columns, uint32_t n_shifts,
+                                    const void* dev_matrix, const uint8_t sum[16],
+                                    const uint8_t column_sum[16], mlh_transcript* tr,
+                                    mlh_shifted_proof* proof) {
+  const uint32_t K = n_shifts;
+  if (!ctx || !prog || !com1 || !dev_matrix || !sum || !column_sum || !tr || !proof ||
+      !proof->sumcheck_polys || !proof->output ||
+      (K && (!shift_columns || !proof->shift_polys || !proof->output2)))
+    return fail(ctx, MLH_ERR_INVALID, "null argument");
+  if (com1->ctx != ctx || (com2 && com2->ctx != ctx))
+    return fail(ctx, MLH_ERR_INVALID, "commitment of another context");
+  const uint32_t Wx = prog->p.width, P1 = com1->width, P2 = com2 ? com2->width : 0;
+  if (!shift_list_ok(Wx, shift_columns, K))
+    return fail(ctx, MLH_ERR_INVALID,
+                "shift list: distinct source columns below W, W + K the program's width, at most 32");
+  const uint32_t W = Wx - K, L = com1->log_height;
+  if (P1 < 1 || P1 + P2 != W || (com2 && com2->log_height != L))
+    return fail(ctx, MLH_ERR_INVALID,
+                "the commitments' widths and n_shifts must add up to the program's width (com2 "
+                "null iff all columns are pre-random), over the same rows");
+  if (W < 32 && (sum_column_mask >> W))
+    return fail(ctx, MLH_ERR_INVALID, "sum column at or above the trace's width");
+  if (h_load(sum) >= kModulus || h_load(column_sum) >= kModulus)
+    return fail(ctx, MLH_ERR_INVALID, "non-canonical sum");
+  // E, the copy of T for the shift reduction and its delta table: pooled, and
+  // back in the pool only after the stream is drained
+  PoolBuf ext(ctx), copy(ctx), succ(ctx);
+  StreamDrain drain(ctx);
+  MLH_TRY(ext.alloc((16ull * Wx) << L));
+  MLH_TRY(mlh_trace_extend_next(ctx, dev_matrix, L, W, shift_columns, K, ext.p));
+  ShiftProve sh = {shift_columns, K, nullptr, nullptr, proof->shift_polys, proof->output2,
+                   &proof->pcs_shift[0], &proof->pcs_shift[1]};
+  if (K) {
+    MLH_TRY(copy.alloc((16ull * W) << L));
+    MLH_TRY(succ.alloc(16ull << L));
+    HIP_TRY(ctx, hipMemcpyAsync(copy.p, dev_matrix, (16ull * W) << L, hipMemcpyDeviceToDevice,
+                                ctx->stream));
+    sh.dev_copy = copy.p;
+    sh.dev_succ = succ.p;
+  }
+  MLH_TRY(system_prove_core(ctx, prog, com1, com2, sum_column_mask, ext.p, sum, column_sum, tr,
+                            proof->sumcheck_polys, proof->output, &proof->pcs[0], &proof->pcs[1],
+                            &sh));
+  proof->log_height = L;
+  proof->width = W;
+  proof->degree = prog->p.degree;
+  proof->pre_random_columns = P1;
+  proof->sum_column_mask = sum_column_mask;
+  proof->n_shifts = K;
+  for (uint32_t k = 0; k < 32; ++k) proof->shift_columns[k] = k < K ? shift_columns[k] : 0u;
   return MLH_OK;
 }
 

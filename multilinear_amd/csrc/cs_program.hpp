@@ -174,6 +174,32 @@ static inline bool cs_decode(const uint8_t* b, uint64_t len, CsProgram& p) {
   return true;
 }
 
+// The program of the shift reduction (mlhip.h, shifted proof, step 7): the one
+// constraint sum_k rand(k) * var(cols[k]) over a width-wide row, declared
+// degree 1, written in the wire format and decoded like a caller's program.
+// n_shifts 1..width, cols[k] < width; false otherwise.
+static inline bool cs_shift_program(uint32_t width, const uint32_t* cols, uint32_t n_shifts,
+                                    CsProgram& p) {
+  if (!cols || n_shifts < 1 || n_shifts > kCsMaxWidth) return false;
+  const uint32_t K = n_shifts, n_instr = 2 * K - 1;
+  const uint32_t hdr[7] = {width, K, 0, K > 1 ? 2u : 1u, n_instr, 1, 1};
+  std::vector<uint8_t> b;
+  for (uint32_t w : hdr)
+    for (uint32_t s = 0; s < 32; s += 8) b.push_back((uint8_t)(w >> s));
+  for (uint32_t k = 0; k < K; ++k) {
+    if (cols[k] >= width) return false;
+    const uint8_t mul[8] = {kCsMul, (uint8_t)(k ? 1 : 0), kCsRand, (uint8_t)k, kCsCol, (uint8_t)cols[k], 0, 0};
+    b.insert(b.end(), mul, mul + 8);
+    if (k) {
+      const uint8_t add[8] = {kCsAdd, 0, kCsTemp, 0, kCsTemp, 1, 0, 0};
+      b.insert(b.end(), add, add + 8);
+    }
+  }
+  b.push_back(kCsTemp);
+  b.push_back(0);
+  return cs_decode(b.data(), b.size(), p);
+}
+
 // ConstraintSet::evaluate (evaluation.rs:21-29): sum_c mask[c] * out_c(values, randoms).
 static inline u128 cs_host_eval(const CsProgram& p, const u128* values, const u128* randoms,
                                 const u128* mask) {

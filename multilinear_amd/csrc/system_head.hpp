@@ -52,4 +52,38 @@ mlh_status system_head(mlh_transcript* tr, const CsProgram& P, uint32_t log_heig
                        const uint8_t root1[32], const uint8_t* root2, uint32_t sum_column_mask,
                        const uint8_t sum[16], const uint8_t* column_sum, SystemHead* out);
 
+// The shift list of a shifted system over a program of width wext = W + K: K
+// distinct source columns below W (K = 0: no list).  Prover and verifier refuse
+// the same lists.
+inline bool shift_list_ok(uint32_t wext, const uint32_t* cols, uint32_t n_shifts) {
+  if (n_shifts >= wext || wext > kCsMaxWidth || (n_shifts && !cols)) return false;
+  const uint32_t W = wext - n_shifts;
+  uint32_t seen = 0;
+  for (uint32_t k = 0; k < n_shifts; ++k) {
+    if (cols[k] >= W || ((seen >> cols[k]) & 1u)) return false;
+    seen |= 1u << cols[k];
+  }
+  return true;
+}
+
+// Step 7's challenge and what both sides derive from it (mlhip.h, shifted
+// proof): absorb the W' elements of `output`, draw lambda, then the randoms
+// lambda^0 .. lambda^(K-1) (LE16 each) and the claim sum_k lambda^k output[W + k].
+// output: canonical elements.
+inline void shift_challenge(mlh_transcript* tr, const uint8_t* output, uint32_t W, uint32_t K,
+                            std::vector<uint8_t>* randoms, uint8_t claim[16]) {
+  mlh_transcript_absorb(tr, output, 16ull * (W + K));
+  uint8_t c[16];
+  mlh_transcript_next_challenge(tr, c);
+  const u128 lambda = h_load(c);
+  randoms->resize(16ull * K);
+  u128 pw = 1, acc = 0;
+  for (uint32_t k = 0; k < K; ++k) {
+    h_store(randoms->data() + 16ull * k, pw);
+    acc = h_add(acc, h_mul(pw, h_load(output + 16ull * (W + k))));
+    pw = h_mul(pw, lambda);
+  }
+  h_store(claim, acc);
+}
+
 }  // namespace mlh

@@ -574,21 +574,28 @@ mlh_status mlh::system_head(mlh_transcript* tr, const CsProgram& P, uint32_t log
 // receives the challenges it derives.
 // smask / beta: the sum columns' term (mlh_cs_sumcheck_verify_sums); sum is
 // then the combined claim.
+// delta_at (optional): the delta table's evaluation at the challenges, handed
+// in by a caller whose table is not eq(row points) -- the shift reduction's
+// succ(rs, .); host_row_points is then not read.  Null: Delta::evaluate of the
+// row points.
+typedef u128 (*DeltaAtFn)(const void* user, const std::vector<u128>& rs);
 static mlh_status cs_sumcheck_verify_rs(const mlh_cs_program* prog, uint32_t log_height,
                                         const uint8_t* host_row_points, const uint8_t* host_randoms,
                                         const uint8_t* host_mask, uint32_t smask, const uint8_t* beta,
                                         const uint8_t sum[16], const uint8_t* polys,
                                         const uint8_t* host_output, mlh_transcript* tr,
-                                        std::vector<u128>* rs_out) {
-  if (!prog || !host_row_points || !host_mask || !sum || !polys || !host_output || !tr ||
-      log_height < 1 || log_height > kCsMaxLogHeight || (prog->p.n_randoms && !host_randoms))
+                                        std::vector<u128>* rs_out, DeltaAtFn delta_at = nullptr,
+                                        const void* delta_user = nullptr) {
+  if (!prog || (!host_row_points && !delta_at) || !host_mask || !sum || !polys || !host_output ||
+      !tr || log_height < 1 || log_height > kCsMaxLogHeight || (prog->p.n_randoms && !host_randoms))
     return MLH_ERR_INVALID;
   const CsProgram& P = prog->p;
   if (smask && (!beta || h_load(beta) >= kModulus || (P.width < 32 && (smask >> P.width))))
     return MLH_ERR_INVALID;
   const uint32_t L = log_height, D = P.points();
   std::vector<u128> row, rnd, mask, output, co;
-  if (!load_canonical(host_row_points, L, row) || !load_canonical(host_randoms, P.n_randoms, rnd) ||
+  if ((!delta_at && !load_canonical(host_row_points, L, row)) ||
+      !load_canonical(host_randoms, P.n_randoms, rnd) ||
       !load_canonical(host_mask, P.n_constraints, mask) || h_load(sum) >= kModulus)
     return MLH_ERR_INVALID;
   if (!load_canonical(host_output, P.width, output) || !load_canonical(polys, L * D, co))
@@ -612,8 +619,11 @@ static mlh_status cs_sumcheck_verify_rs(const mlh_cs_program* prog, uint32_t log
     claim = horner(pol, r);
   }
   u128 delta = 1;  // Delta::evaluate (evaluation.rs:80-90)
-  for (uint32_t i = 0; i < L; ++i)
-    delta = h_mul(delta, h_add(h_mul(row[i], rs[i]), h_mul(h_sub(1, row[i]), h_sub(1, rs[i]))));
+  if (delta_at)
+    delta = delta_at(delta_user, rs);
+  else
+    for (uint32_t i = 0; i < L; ++i)
+      delta = h_mul(delta, h_add(h_mul(row[i], rs[i]), h_mul(h_sub(1, row[i]), h_sub(1, rs[i]))));
   const u128 comp = cs_host_eval(P, output.data(), rnd.data(), mask.data());
   u128 lin = 0;  // beta * sum_{j in S} output[j]
   if (smask) {
@@ -627,31 +637,83 @@ static mlh_status cs_sumcheck_verify_rs(const mlh_cs_program* prog, uint32_t log
   return MLH_OK;
 }
 
-// What follows the header checks of both system verifiers: the head, the
-// sumcheck against the claimed output, then the opening(s) at its rs -- pcs1 for
-// the first pcs1->fri.num_codes columns, pcs2 (null: one phase) for the rest.
-// Every rejection is MLH_ERR_VERIFY with the transcript as at entry.
+// succ(x, y) = sum_i eq(x, i) eq(y, (i + 1) mod 2^n) in closed form (mlhip.h):
+// bit b of the row index <-> point[n - 1 - b].  One pass from the top bit down
+// for the suffix products of (x_b y_b + (1 - x_b)(1 - y_b)), one from bit 0 up
+// with the running product of x_b (1 - y_b).
+static u128 succ_evaluate(const u128* x, const u128* y, uint32_t n) {
+  std::vector<u128> hi(n + 1, 1);  // hi[k] = prod_{b >= k} eq1(x_b, y_b)
+  for (uint32_t k = n; k-- > 0;) {
+    const u128 xb = x[n - 1 - k], yb = y[n - 1 - k];
+    hi[k] = h_mul(hi[k + 1], h_add(h_mul(xb, yb), h_mul(h_sub(1, xb), h_sub(1, yb))));
+  }
+  u128 low = 1, acc = 0;  // low = prod_{b < k} x_b (1 - y_b)
+  for (uint32_t k = 0; k < n; ++k) {
+    const u128 xb = x[n - 1 - k], yb = y[n - 1 - k];
+    acc = h_add(acc, h_mul(h_mul(low, h_mul(h_sub(1, xb), yb)), hi[k + 1]));
+    low = h_mul(low, h_mul(xb, h_sub(1, yb)));
+  }
+  return h_add(acc, low);  // the wrap: all ones -> all zeros
+}
+static u128 succ_at(const void* user, const std::vector<u128>& rs2) {
+  const std::vector<u128>& rs = *static_cast<const std::vector<u128>*>(user);
+  return succ_evaluate(rs.data(), rs2.data(), (uint32_t)rs.size());
+}
+
+// The shift part of a shifted proof as the verifier core sees it (null: none,
+// or K = 0).
+struct ShiftVerify {
+  const uint32_t* cols;
+  uint32_t K;
+  const uint8_t* polys;    // [L][2][16]
+  const uint8_t* output2;  // [W][16]
+  const mlh_batched_pcs_proof* pcs1;
+  const mlh_batched_pcs_proof* pcs2;  // null: one phase
+};
+
+// What follows the header checks of the system verifiers: the head, the
+// sumcheck against the claimed output, the shift reduction (sh; mlhip.h, step
+// 7), then the opening(s) at its rs -- pcs1 for the first pcs1->fri.num_codes
+// columns, pcs2 (null: one phase) for the rest -- and, with sh, those of the
+// same columns at rs'.  Every rejection is MLH_ERR_VERIFY with the transcript
+// as at entry.
 static mlh_status system_verify_core(const mlh_cs_program* prog, uint32_t L, uint32_t sum_column_mask,
                                      const uint8_t sum[16], const uint8_t* column_sum,
                                      const uint8_t* polys, const uint8_t* output,
                                      const mlh_batched_pcs_proof* pcs1,
-                                     const mlh_batched_pcs_proof* pcs2, mlh_transcript* tr) {
+                                     const mlh_batched_pcs_proof* pcs2, mlh_transcript* tr,
+                                     const ShiftVerify* sh = nullptr) {
   TranscriptGuard guard(tr);
   SystemHead h(prog->p, L);
-  std::vector<u128> rs;
+  std::vector<u128> rs, rs2;
   mlh_status st = system_head(tr, prog->p, L, pcs1->fri.batch_commitment,
                               pcs2 ? pcs2->fri.batch_commitment : nullptr, sum_column_mask, sum,
                               column_sum, &h);
   if (st == MLH_OK)
     st = cs_sumcheck_verify_rs(prog, L, h.row.data(), h.randoms.data(), h.mask.data(),
                                sum_column_mask, h.beta, h.claim, polys, output, tr, &rs);
-  if (st == MLH_OK) {
-    std::vector<uint8_t> in(16ull * L);
-    for (uint32_t i = 0; i < L; ++i) h_store(in.data() + 16ull * i, rs[i]);
-    st = mlh_batched_pcs_verify(pcs1, L, in.data(), output, tr);
-    if (st == MLH_OK && pcs2)
-      st = mlh_batched_pcs_verify(pcs2, L, in.data(), output + 16ull * pcs1->fri.num_codes, tr);
+  const uint32_t P1 = pcs1->fri.num_codes;
+  if (st == MLH_OK && sh) {
+    const uint32_t W = prog->p.width - sh->K;
+    mlh_cs_program sp;
+    std::vector<uint8_t> lambdas;
+    uint8_t claim2[16], one[16];
+    h_store(one, 1);
+    if (!cs_shift_program(W, sh->cols, sh->K, sp.p)) return MLH_ERR_VERIFY;
+    shift_challenge(tr, output, W, sh->K, &lambdas, claim2);
+    st = cs_sumcheck_verify_rs(&sp, L, nullptr, lambdas.data(), one, 0, nullptr, claim2, sh->polys,
+                               sh->output2, tr, &rs2, succ_at, &rs);
   }
+  std::vector<uint8_t> in(16ull * L);
+  const auto open = [&](const std::vector<u128>& at, const uint8_t* out,
+                        const mlh_batched_pcs_proof* a, const mlh_batched_pcs_proof* b) {
+    for (uint32_t i = 0; i < L; ++i) h_store(in.data() + 16ull * i, at[i]);
+    mlh_status s = mlh_batched_pcs_verify(a, L, in.data(), out, tr);
+    if (s == MLH_OK && b) s = mlh_batched_pcs_verify(b, L, in.data(), out + 16ull * P1, tr);
+    return s;
+  };
+  if (st == MLH_OK) st = open(rs, output, pcs1, pcs2);
+  if (st == MLH_OK && sh) st = open(rs2, sh->output2, sh->pcs1, sh->pcs2);
   if (st != MLH_OK) return MLH_ERR_VERIFY;
   guard.keep();
   return MLH_OK;
@@ -710,6 +772,49 @@ mlh_status mlh_system_verify_phased(const mlh_cs_program* prog, uint32_t log_hei
     return MLH_ERR_VERIFY;
   return system_verify_core(prog, L, sum_column_mask, sum, column_sum, proof->sumcheck_polys,
                             proof->output, &proof->pcs[0], P1 < W ? &proof->pcs[1] : nullptr, tr);
+}
+
+mlh_status mlh_shift_succ_evaluate(const uint8_t* x, const uint8_t* y, uint32_t n, uint8_t out[16]) {
+  if (!out || n > 64 || (n && (!x || !y))) return MLH_ERR_INVALID;
+  std::vector<u128> xv, yv;
+  if (!load_canonical(x, n, xv) || !load_canonical(y, n, yv)) return MLH_ERR_INVALID;
+  h_store(out, succ_evaluate(xv.data(), yv.data(), n));
+  return MLH_OK;
+}
+
+mlh_status mlh_system_verify_shifted(const mlh_cs_program* prog, uint32_t log_height,
+                                     uint32_t pre_random_columns, uint32_t sum_column_mask,
+                                     const uint32_t* shift_columns, uint32_t n_shifts,
+                                     const uint8_t sum[16], const uint8_t column_sum[16],
+                                     const mlh_shifted_proof* proof, mlh_transcript* tr) {
+  const uint32_t K = n_shifts;
+  if (!prog || !sum || !column_sum || !proof || !tr || !proof->sumcheck_polys || !proof->output ||
+      !proof->pcs[0].sumcheck_polys || (K && !shift_columns) ||
+      !shift_list_ok(prog->p.width, shift_columns, K))
+    return MLH_ERR_INVALID;
+  const CsProgram& P = prog->p;
+  const uint32_t L = log_height, W = P.width - K, P1 = pre_random_columns;
+  const bool two = P1 < W;
+  if (L < 1 || L > kCsMaxLogHeight || P1 < 1 || P1 > W || (W < 32 && (sum_column_mask >> W)) ||
+      proof->log_height != L || proof->width != W || proof->degree != P.degree ||
+      proof->pre_random_columns != P1 || proof->sum_column_mask != sum_column_mask ||
+      proof->n_shifts != K || proof->pcs[0].fri.num_codes != P1 ||
+      (two && (!proof->pcs[1].sumcheck_polys || proof->pcs[1].fri.num_codes != W - P1)) ||
+      h_load(sum) >= kModulus || h_load(column_sum) >= kModulus)
+    return MLH_ERR_VERIFY;
+  for (uint32_t k = 0; k < 32; ++k)
+    if (proof->shift_columns[k] != (k < K ? shift_columns[k] : 0u)) return MLH_ERR_VERIFY;
+  if (!K)
+    return system_verify_core(prog, L, sum_column_mask, sum, column_sum, proof->sumcheck_polys,
+                              proof->output, &proof->pcs[0], two ? &proof->pcs[1] : nullptr, tr);
+  if (!proof->shift_polys || !proof->output2 || !proof->pcs_shift[0].sumcheck_polys ||
+      proof->pcs_shift[0].fri.num_codes != P1 ||
+      (two && (!proof->pcs_shift[1].sumcheck_polys || proof->pcs_shift[1].fri.num_codes != W - P1)))
+    return MLH_ERR_VERIFY;
+  const ShiftVerify sh = {shift_columns, K, proof->shift_polys, proof->output2, &proof->pcs_shift[0],
+                          two ? &proof->pcs_shift[1] : nullptr};
+  return system_verify_core(prog, L, sum_column_mask, sum, column_sum, proof->sumcheck_polys,
+                            proof->output, &proof->pcs[0], two ? &proof->pcs[1] : nullptr, tr, &sh);
 }
 
 }  // extern "C"
