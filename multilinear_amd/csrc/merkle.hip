@@ -168,14 +168,6 @@ level2_kernel(const uint8_t* __restrict__ child, uint8_t* __restrict__ parent,
   digest_store(grand + j * 32, sha256_node(p0, p1));
 }
 
-__global__ void __launch_bounds__(256)
-level1_kernel(const uint8_t* __restrict__ child, uint8_t* __restrict__ parent, uint64_t nparent) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= nparent) return;
-  const Sha256State a = digest_load(child + j * 64), b = digest_load(child + j * 64 + 32);
-  digest_store(parent + j * 32, sha256_node(a, b));
-}
-
 // Finish a level of n <= 1024 digests (n a power of two >= 2) to the root in
 // one workgroup; writes every level into `out` consecutively.  ra.t: wave 0
 // then absorbs the root (and ra.poly_in) into the device transcript
@@ -276,18 +268,12 @@ hipError_t launch_merkle_levels_from(uint8_t* layers, uint64_t off, uint64_t n, 
   while (n > kTailLevel) {
     uint8_t* child = layers + off * 32;
     uint8_t* parent = child + n * 32;
-    if (n >= 4 * 1024) {
-      uint8_t* grand = parent + (n / 2) * 32;
-      hipLaunchKernelGGL(level2_kernel, dim3(blocks_for(n / 4, 256)), dim3(256), 0, st, child,
-                         parent, grand, n / 4);
-      off += n + n / 2;
-      n /= 4;
-    } else {
-      hipLaunchKernelGGL(level1_kernel, dim3(blocks_for(n / 2, 256)), dim3(256), 0, st, child,
-                         parent, n / 2);
-      off += n;
-      n /= 2;
-    }
+    uint8_t* grand = parent + (n / 2) * 32;
+    // n > 2^18 is a multiple of 4: two levels per launch
+    hipLaunchKernelGGL(level2_kernel, dim3(blocks_for(n / 4, 256)), dim3(256), 0, st, child, parent,
+                       grand, n / 4);
+    off += n + n / 2;
+    n /= 4;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
