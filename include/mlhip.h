@@ -814,7 +814,8 @@ mlh_status mlh_system_verify_phased(const mlh_cs_program* prog, uint32_t log_hei
  * for next(c_k); the list travels beside the program, whose wire format is
  * unchanged.  A constraint that should not hold across the wrap from the last
  * row to row 0 is gated by a selector column of the caller's, e.g.
- * (1 - last) * (next(a) - a - b).  The sumcheck folds rows pairwise, so "the
+ * (1 - last) * (next(a) - a - b); such a selector belongs in a public column
+ * (below), where the verifier derives it.  The sumcheck folds rows pairwise, so "the
  * next row" is a protocol step and no addressing mode.  Transcript order, on
  * top of the two-phase proof's:
  *   1-5. as mlh_system_prove_phased (the program's randoms and constraints);
@@ -911,6 +912,118 @@ mlh_status mlh_system_verify_shifted(const mlh_cs_program* prog, uint32_t log_he
                                      const uint32_t* shift_columns, uint32_t n_shifts,
                                      const uint8_t sum[16], const uint8_t column_sum[16],
                                      const mlh_shifted_proof* proof, mlh_transcript* tr);
+
+/* ---- public columns: selectors, constants and inputs the verifier derives ---- *
+ * The last F columns of a W-wide trace, [W - F, W), are public: they have a
+ * short description (the spec), the prover neither commits nor opens them, and
+ * the verifier evaluates their multilinear extensions itself, in closed form.
+ * The committed phases are [0, P) and [P, W - F).  A selector such as the wrap
+ * gate `last` of (1 - last) * (next(a) - a - b), a public input tied to a row,
+ * a round constant or the row index belongs here: as a committed column it is
+ * the prover's to choose.
+ *
+ * Wire format of a spec (all integers little-endian u32 unless stated; elements
+ * LE16 and canonical; 1 <= F <= 16):
+ *   header   2 x u32: F, 0 (reserved)
+ *   per column, in order: u32 kind, u32 arg, payload
+ *     0 CONST     arg 0           1 element c             row i holds c
+ *     1 FIRST     arg 0           -                       1 at row 0, else 0
+ *     2 LAST      arg 0           -                       1 at row H - 1, else 0
+ *     3 ROW       arg 0           -                       row i holds i
+ *     4 PERIODIC  arg k (0..16)   2^k elements v          row i holds v[i mod 2^k]
+ *     5 SPARSE    arg m (1..4096) m x (u64 row, element)  rows strictly increasing;
+ *                                                         0 elsewhere
+ * Exactly one byte string per spec: MLH_ERR_INVALID for an unknown kind, a
+ * nonzero reserved word or arg (kinds 0-3), a non-canonical element, unsorted
+ * or repeated sparse rows, a short buffer, trailing bytes.  Where the height
+ * 2^L is known a spec must fit it, else MLH_ERR_INVALID: every PERIODIC k <= L
+ * and every SPARSE row < 2^L.  The handle belongs to no context and is host
+ * only. */
+typedef struct mlh_public_columns mlh_public_columns;
+mlh_status mlh_public_columns_create(const uint8_t* wire, uint64_t len, mlh_public_columns** out);
+void mlh_public_columns_destroy(mlh_public_columns* spec);
+uint32_t mlh_public_columns_count(const mlh_public_columns* spec); /* F; 0 for null */
+/* SHA-256 of the wire bytes, computed once at create. */
+mlh_status mlh_public_columns_digest(const mlh_public_columns* spec, uint8_t out[32]);
+/* out[j] = the multilinear extension of column j over 2^log_height rows at
+ * point (log_height canonical elements; log_height 0..32), host only, in
+ * O(log H) field operations per column (PERIODIC: O(2^k); SPARSE: O(m log H)).
+ * With x_b = point[log_height - 1 - b] the coordinate of bit b of the row
+ * index (Mask::evaluate's order, evaluation.rs:56-73):
+ *   CONST     c
+ *   FIRST     prod_b (1 - x_b)
+ *   LAST      prod_b x_b
+ *   ROW       sum_b 2^b x_b
+ *   PERIODIC  the extension of v at point[L - k : L], the 2^k-entry table folded
+ *             in the same bit order; v[0] for k = 0
+ *   SPARSE    sum_m v_m eq(point, row_m)
+ * MLH_ERR_INVALID for a null pointer, a spec that does not fit log_height or a
+ * non-canonical point. */
+mlh_status mlh_public_columns_evaluate(const mlh_public_columns* spec, uint32_t log_height,
+                                       const uint8_t* point, uint8_t* out);
+/* Writes columns [width - F, width) of the row-major 2^log_height x width
+ * dev_matrix in place and touches no other byte: a strip kernel (256 threads,
+ * at most 1024 blocks, a block loops over tiles of tile_rows rows, 16-byte
+ * stores in runs of 16 F bytes per row) and, with SPARSE columns, a scatter
+ * kernel behind it on the context stream.  The periodic tables and sparse
+ * entries reach the device once per call, through the context pool.  width
+ * 1..32, F <= width, log_height 0..32 (with one row, that row is both first
+ * and last); MLH_ERR_INVALID for a null pointer, these limits or a spec that
+ * does not fit log_height, with the matrix untouched. */
+mlh_status mlh_trace_fill_public(mlh_ctx* ctx, const mlh_public_columns* spec, void* dev_matrix,
+                                 uint32_t log_height, uint32_t width);
+/* Its launch shape for n_public = F columns: the rows a block writes per tile
+ * (a power of two with tile_rows * F <= 2048, at most the height) and the
+ * number of blocks; a block visits ceil(tiles / blocks) tiles. */
+mlh_status mlh_trace_fill_public_launch_info(uint32_t log_height, uint32_t width, uint32_t n_public,
+                                             uint32_t* tile_rows, uint32_t* blocks);
+/* mlh_system_prove_shifted with public columns.  mlh_shifted_proof is reused
+ * unchanged: width = W with the public columns included, output is [W + K],
+ * output2 is [W].  Transcript order:
+ *   0. only if F > 0: absorb the 32-byte digest of the spec;
+ *   1-5. as mlh_system_prove_shifted; commitment1 covers [0, P), commitment2
+ *      [P, W - F) and is null iff P = W - F: P1 + P2 + F = W, W the program's
+ *      width minus K;
+ *   6-7. unchanged: the sumcheck and the shift reduction run on all W columns; a
+ *      public column may be a shift source or a sum column;
+ *   8. the openings cover the committed columns only: output[0:P] on commitment
+ *      1 and output[P:W-F] on commitment 2 at rs, and with K > 0 the same of
+ *      output2 at rs'.
+ * The verifier, after each sumcheck and before the openings, computes
+ * mlh_public_columns_evaluate(spec, L, rs) and rejects unless it equals
+ * output[W-F:W] element for element, and with K > 0 the same at rs' against
+ * output2[W-F:W]: all F columns at both points, whether or not a constraint
+ * reads them -- nothing in the proof stays unbound.  With spec null (F = 0) the
+ * proof bytes and the final transcript state are mlh_system_prove_shifted's.
+ * A caller who needs the trace randoms before phase 2
+ * (mlh_system_trace_randoms) absorbs the digest into a clone of the transcript
+ * first: the randoms are drawn behind step 0.
+ *
+ * The prover does not check that the strip of dev_matrix (see
+ * mlh_trace_fill_public) equals the spec: like a broken constraint, a wrong
+ * strip returns MLH_OK and the verifier rejects.  MLH_ERR_INVALID, with the
+ * transcript as at entry, for every argument error of the shifted call and for
+ * F >= W, widths that do not add up (a commitment2 given although P = W - F
+ * included) and a spec that does not fit the height. */
+mlh_status mlh_system_prove_public(mlh_ctx* ctx, const mlh_cs_program* prog,
+                                   const mlh_trace_commitment* commitment1,
+                                   const mlh_trace_commitment* commitment2,
+                                   uint32_t sum_column_mask, const uint32_t* shift_columns,
+                                   uint32_t n_shifts, const mlh_public_columns* spec,
+                                   const void* dev_matrix, const uint8_t sum[16],
+                                   const uint8_t column_sum[16], mlh_transcript* tr,
+                                   mlh_shifted_proof* proof);
+/* The verifier, host only and trace-less, in the same order.  MLH_ERR_INVALID
+ * for a null pointer, a shift list the prover would refuse, F >= W or a spec
+ * that does not fit log_height; MLH_ERR_VERIFY for every rejection of the
+ * proof, as mlh_system_verify_shifted.  In both cases the transcript is as at
+ * entry; on MLH_OK it ends in the prover's state. */
+mlh_status mlh_system_verify_public(const mlh_cs_program* prog, uint32_t log_height,
+                                    uint32_t pre_random_columns, uint32_t sum_column_mask,
+                                    const uint32_t* shift_columns, uint32_t n_shifts,
+                                    const mlh_public_columns* spec, const uint8_t sum[16],
+                                    const uint8_t column_sum[16], const mlh_shifted_proof* proof,
+                                    mlh_transcript* tr);
 
 /* ---- phase 2 on the device: fill programs and the column sum --------------- *
  * Between mlh_system_trace_randoms and mlh_trace_commit_range of the columns

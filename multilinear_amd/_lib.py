@@ -280,6 +280,18 @@ SIGNATURES = {
                                       _P, ctypes.POINTER(ShiftedProofC)]),
     "mlh_system_verify_shifted": (_I, [_P, _U32, _U32, _U32, ctypes.POINTER(_U32), _U32, _P, _P,
                                        ctypes.POINTER(ShiftedProofC), _P]),
+    "mlh_public_columns_create": (_I, [_P, _U64, ctypes.POINTER(_P)]),
+    "mlh_public_columns_destroy": (None, [_P]),
+    "mlh_public_columns_count": (_U32, [_P]),
+    "mlh_public_columns_digest": (_I, [_P, _P]),
+    "mlh_public_columns_evaluate": (_I, [_P, _U32, _P, _P]),
+    "mlh_trace_fill_public": (_I, [_P, _P, _P, _U32, _U32]),
+    "mlh_trace_fill_public_launch_info": (_I, [_U32, _U32, _U32, ctypes.POINTER(_U32),
+                                               ctypes.POINTER(_U32)]),
+    "mlh_system_prove_public": (_I, [_P, _P, _P, _P, _U32, ctypes.POINTER(_U32), _U32, _P, _P, _P, _P,
+                                     _P, ctypes.POINTER(ShiftedProofC)]),
+    "mlh_system_verify_public": (_I, [_P, _U32, _U32, _U32, ctypes.POINTER(_U32), _U32, _P, _P, _P,
+                                      ctypes.POINTER(ShiftedProofC), _P]),
     "mlh_fill_program_create": (_I, [_P, _U64, ctypes.POINTER(_P)]),
     "mlh_fill_program_destroy": (None, [_P]),
     "mlh_fill_program_width": (_U32, [_P]),

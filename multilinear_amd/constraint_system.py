@@ -21,7 +21,13 @@ mlh_system_prove_phased / _verify_phased, the column sum by default from
 mlh_trace_column_sum.  A constraint set may refer to the next row with
 ``nxt(j)`` (a shifted system: ``compile_shifted``, ``Trace.extend_next``);
 ``PhasedProver.prove`` then runs mlh_system_prove_shifted and returns a
-``ShiftedSystemProof``.  A lookup's multiplicity column, which is pre-random, is
+``ShiftedSystemProof``.  The last columns of a layout may be public
+(``WitnessLayout(public_columns=PublicColumns()...)``: selectors, constants,
+the row index, periodic tables, sparse public inputs): ``phased_prover`` writes
+them with ``Trace.fill_public`` (mlh_trace_fill_public), commits only the
+columns below them and proves with mlh_system_prove_public, and
+``ShiftedSystemProof.verify`` evaluates the spec itself
+(mlh_system_verify_public).  A lookup's multiplicity column, which is pre-random, is
 counted in place before ``phased_prover`` by ``Trace.lookup_multiplicities``
 (mlh_trace_lookup_counts), or, for keys of several columns such as (x, y, x ^ y),
 by ``Trace.lookup_tuple_multiplicities`` (mlh_trace_lookup_tuple_counts);
@@ -335,6 +341,109 @@ class Program:
         return t.value, b.value
 
 
+PC_CONST, PC_FIRST, PC_LAST, PC_ROW, PC_PERIODIC, PC_SPARSE = 0, 1, 2, 3, 4, 5
+
+
+def _le16(v):
+    return (int(v) % M).to_bytes(16, "little")
+
+
+class PublicColumns:
+    """The public columns of a trace, its last ``len(self)`` ones: columns with
+    a short description that the prover neither commits nor opens and the
+    verifier evaluates itself (mlh_public_columns, include/mlhip.h).  A builder:
+    each call appends one column and returns the builder.  ``wire`` is the
+    encoded spec; the handle behind ``h`` is made from it on first use and
+    needs no GPU."""
+
+    def __init__(self):
+        self._cols = []  # (kind, arg, payload bytes)
+        self._handle = None
+
+    def _add(self, kind, arg, payload=b""):
+        if self._handle is not None:
+            raise ValueError("the spec is in use: build a new one")
+        self._cols.append((kind, arg, payload))
+        return self
+
+    def const(self, c):
+        """Every row holds c."""
+        return self._add(PC_CONST, 0, _le16(c))
+
+    def first(self):
+        """1 at row 0, else 0."""
+        return self._add(PC_FIRST, 0)
+
+    def last(self):
+        """1 at the last row, else 0."""
+        return self._add(PC_LAST, 0)
+
+    def row_index(self):
+        """Row i holds i."""
+        return self._add(PC_ROW, 0)
+
+    def periodic(self, values):
+        """Row i holds values[i mod len(values)]; the length is a power of two."""
+        values = list(values)
+        n = len(values)
+        if n < 1 or n & (n - 1):
+            raise ValueError("a periodic column takes a power-of-two number of values")
+        return self._add(PC_PERIODIC, n.bit_length() - 1, b"".join(_le16(v) for v in values))
+
+    def sparse(self, entries):
+        """{row: value}; zero on every other row."""
+        items = sorted((int(r), v) for r, v in dict(entries).items())
+        return self._add(PC_SPARSE, len(items),
+                         b"".join(struct.pack("<Q", r) + _le16(v) for r, v in items))
+
+    def __len__(self):
+        return len(self._cols)
+
+    @property
+    def wire(self):
+        return struct.pack("<2I", len(self._cols), 0) + b"".join(
+            struct.pack("<2I", kind, arg) + payload for kind, arg, payload in self._cols)
+
+    @property
+    def h(self):
+        if self._handle is None:
+            w = self.wire
+            h = ctypes.c_void_p()
+            buf = (ctypes.c_uint8 * len(w)).from_buffer_copy(w)
+            check(lib().mlh_public_columns_create(buf, len(w), ctypes.byref(h)))
+            self._handle = h.value
+        return self._handle
+
+    def __del__(self):
+        try:
+            if self._handle is not None:
+                lib().mlh_public_columns_destroy(self._handle)
+        except Exception:
+            pass
+
+    @property
+    def digest(self):
+        out = (ctypes.c_uint8 * 32)()
+        check(lib().mlh_public_columns_digest(self.h, out))
+        return bytes(out)
+
+    def evaluate(self, point):
+        """The columns' multilinear extensions over 2^len(point) rows at
+        ``point``, on the host (mlh_public_columns_evaluate)."""
+        point = list(point)
+        out = (ctypes.c_uint8 * (16 * len(self)))()
+        check(lib().mlh_public_columns_evaluate(self.h, len(point), _elems(point), out))
+        return _split(out, len(self))
+
+
+def public_fill_launch_info(log_height, width, n_public):
+    """(rows per tile, blocks) of mlh_trace_fill_public."""
+    rows, blocks = ctypes.c_uint32(), ctypes.c_uint32()
+    check(lib().mlh_trace_fill_public_launch_info(log_height, width, n_public, ctypes.byref(rows),
+                                                  ctypes.byref(blocks)))
+    return rows.value, blocks.value
+
+
 def _elems(vals):
     vals = list(vals)
     if not vals:
@@ -365,13 +474,23 @@ class ConstraintSet:
 
 
 class WitnessLayout:
-    """system.rs:17-30."""
+    """system.rs:17-30.  public_columns (a PublicColumns; None: none): the last
+    len(public_columns) of ``columns`` are public -- not committed, derived by
+    the verifier."""
 
-    def __init__(self, columns, randoms=0, pre_random_columns=0, sum_columns=()):
+    def __init__(self, columns, randoms=0, pre_random_columns=0, sum_columns=(),
+                 public_columns=None):
         self.columns = columns
         self.randoms = randoms
         self.pre_random_columns = pre_random_columns
         self.sum_columns = tuple(sum_columns)
+        if public_columns is not None and not len(public_columns):
+            public_columns = None  # an empty builder: no public columns
+        self.public_columns = public_columns
+
+    @property
+    def n_public(self):
+        return len(self.public_columns) if self.public_columns is not None else 0
 
 
 class Trace:
@@ -415,6 +534,14 @@ class Trace:
         check(lib().mlh_trace_fill(ctx, prog.h, ptr(self._matrix), self._height.bit_length() - 1,
                                    self._width, _elems(randoms)), ctx)
         return prog
+
+    def fill_public(self, spec, device=0):
+        """Write the public columns ``spec`` (a PublicColumns) into the last
+        len(spec) columns of every row, in place (mlh_trace_fill_public)."""
+        ctx = context(device)
+        check(lib().mlh_trace_fill_public(ctx, spec.h, ptr(self._matrix),
+                                          self._height.bit_length() - 1, self._width), ctx)
+        return spec
 
     def extend_next(self, shift_columns, device=0):
         """The extension of a shifted system (mlh_trace_extend_next): a new
@@ -821,8 +948,9 @@ class ShiftedSystemProof(_ProofHolder):
     and the openings of both commitments at rs and at rs'."""
 
     def __init__(self, log_height, width, degree, pre_random_columns, sum_column_mask,
-                 shift_columns):
+                 shift_columns, n_public=0):
         super().__init__(_lib.ShiftedProofC(), log_height, width, degree)
+        self.n_public = n_public
         self.pre_random_columns, self.sum_column_mask = pre_random_columns, sum_column_mask
         self.shift_columns = [int(c) for c in shift_columns]
         K, P, c = len(self.shift_columns), pre_random_columns, self.c
@@ -835,7 +963,8 @@ class ShiftedSystemProof(_ProofHolder):
         c.pre_random_columns, c.sum_column_mask, c.n_shifts = P, sum_column_mask, K
         for k, col in enumerate(self.shift_columns):
             c.shift_columns[k] = col
-        widths = [P] + ([width - P] if P < width else [])
+        committed = width - n_public  # the openings leave the public columns out
+        widths = [P] + ([committed - P] if P < committed else [])
         self.pcs = [BatchedPCSProof(log_height, w) for w in widths]
         self.pcs_shift = [BatchedPCSProof(log_height, w) for w in widths] if K else []
         for i, p in enumerate(self.pcs):
@@ -866,34 +995,52 @@ class ShiftedSystemProof(_ProofHolder):
     def output2(self):
         return _split(self._output2, self.width) if self.shift_columns else []
 
-    def verify(self, transcript, constraints, layout, total_sum, column_sum):
-        """mlh_system_verify_shifted, host only: True iff accepted.  The
+    def verify(self, transcript, constraints, layout, total_sum, column_sum, public=None):
+        """mlh_system_verify_public (without public columns:
+        mlh_system_verify_shifted), host only: True iff accepted.  The
         constraint set is the prover's, with its ``nxt`` columns; the transcript
-        is the one the prover started from and is advanced only on True."""
+        is the one the prover started from and is advanced only on True.
+        public (a PublicColumns; None: the layout's): the verifier's own spec of
+        the public columns."""
         prog, shifts = _shifted_program_of(constraints, layout)
         arr = (ctypes.c_uint32 * max(len(shifts), 1))(*shifts)
-        return lib().mlh_system_verify_shifted(prog.h, self.log_height, layout.pre_random_columns,
-                                               _column_mask(layout), arr, len(shifts),
-                                               fe_bytes(total_sum), fe_bytes(column_sum),
-                                               ctypes.byref(self.c), transcript.h) == 0
+        if public is None:
+            public = getattr(layout, "public_columns", None)
+        return lib().mlh_system_verify_public(prog.h, self.log_height, layout.pre_random_columns,
+                                              _column_mask(layout), arr, len(shifts),
+                                              public.h if public is not None and len(public) else None,
+                                              fe_bytes(total_sum), fe_bytes(column_sum),
+                                              ctypes.byref(self.c), transcript.h) == 0
 
 
 class PhasedProver:
     """System::prover for a layout with pre_random_columns / sum_columns
     (system.rs:17-30, 56-72): holds the commitment to columns [0, P) and the
     trace randoms drawn after it; ``prove`` commits to the other columns of
-    the matrix as it then stands."""
+    the matrix as it then stands.  With public columns in the layout (its last
+    ones) the strip is filled here, before the first commitment, the
+    commitments cover the columns below it, and ``prove`` runs
+    mlh_system_prove_public."""
 
     def __init__(self, transcript, constraints, layout, trace, device=0):
         P, W = layout.pre_random_columns, layout.columns
-        if not 1 <= P <= W or W != trace.width():
-            raise ValueError("pre_random_columns must be in 1..columns, columns the trace's width")
+        self._public = getattr(layout, "public_columns", None)
+        self._committed = W - (len(self._public) if self._public is not None else 0)
+        if not 1 <= P <= self._committed or W != trace.width():
+            raise ValueError("pre_random_columns must be in 1..columns less the public ones, "
+                             "columns the trace's width")
         self._constraints, self._layout, self._trace, self._device = constraints, layout, trace, device
         self._mask = _column_mask(layout)
         self.program, self.shift_columns = _shifted_program_of(constraints, layout)
+        if self._public is not None:
+            trace.fill_public(self._public, device)
         self._com1 = Commitment.new(trace, device, columns=(0, P))
         out = (ctypes.c_uint8 * (16 * max(layout.randoms, 1)))()
-        check(lib().mlh_system_trace_randoms(transcript.h, self._com1.root(), layout.randoms, out))
+        head = transcript
+        if self._public is not None:  # step 0: the spec's digest comes before the root
+            head = transcript.clone()
+            head.absorb(self._public.digest)
+        check(lib().mlh_system_trace_randoms(head.h, self._com1.root(), layout.randoms, out))
         self.randoms = _split(out, layout.randoms)
         self._entry = transcript.random()
 
@@ -924,17 +1071,20 @@ class PhasedProver:
         if column_sum is None:
             column_sum = trace_column_sum(t.matrix(), W, lay.sum_columns, self._device)
         self.column_sum = column_sum
-        com2 = Commitment.new(t, self._device, columns=(P, W - P)) if P < W else None
-        if self.shift_columns:  # a shifted constraint set: the trace itself is not modified
+        C = self._committed
+        com2 = Commitment.new(t, self._device, columns=(P, C - P)) if P < C else None
+        if self.shift_columns or self._public is not None:
+            # a shifted constraint set or public columns: the trace itself is not modified
             K = len(self.shift_columns)
             p = ShiftedSystemProof(self._com1.log_height, W, self._constraints.degree(), P,
-                                   self._mask, self.shift_columns)
-            check(lib().mlh_system_prove_shifted(ctx, self.program.h, self._com1.h,
-                                                 com2.h if com2 else None, self._mask,
-                                                 (ctypes.c_uint32 * K)(*self.shift_columns), K,
-                                                 ptr(t.matrix()), fe_bytes(total_sum),
-                                                 fe_bytes(column_sum), transcript.h,
-                                                 ctypes.byref(p.c)), ctx)
+                                   self._mask, self.shift_columns, W - C)
+            check(lib().mlh_system_prove_public(ctx, self.program.h, self._com1.h,
+                                                com2.h if com2 else None, self._mask,
+                                                (ctypes.c_uint32 * max(K, 1))(*self.shift_columns), K,
+                                                self._public.h if self._public is not None else None,
+                                                ptr(t.matrix()), fe_bytes(total_sum),
+                                                fe_bytes(column_sum), transcript.h,
+                                                ctypes.byref(p.c)), ctx)
             p._sync()
             return p
         p = PhasedSystemProof(self._com1.log_height, W, self._constraints.degree(), P, self._mask)

@@ -49,6 +49,7 @@
 #include "trace_commit.hpp"
 #include "trace_fill.hpp"
 #include "trace_lookup.hpp"
+#include "trace_public.hpp"
 #include "trace_shift.hpp"
 #include "transcript_dev.hpp"
 
@@ -1625,6 +1626,9 @@ struct ShiftProve {
 // + K columns wide, and after the sumcheck comes the shift reduction on
 // sh->dev_copy (mlhip.h, step 7) and, behind the openings at rs, those of the
 // same handles at rs'.
+// public_digest (null: none): the digest of the public columns' spec, absorbed
+// first (step 0); the handles then cover the columns below the public ones, and
+// the openings, which take the handles' widths, leave those out.
 static mlh_status system_prove_core(mlh_ctx* ctx, const mlh_cs_program* prog,
                                     const mlh_trace_commitment* com1,
                                     const mlh_trace_commitment* com2, uint32_t sum_column_mask,
@@ -1632,12 +1636,13 @@ static mlh_status system_prove_core(mlh_ctx* ctx, const mlh_cs_program* prog,
                                     const uint8_t* column_sum, mlh_transcript* tr,
                                     uint8_t* polys_out, uint8_t* output_out,
                                     mlh_batched_pcs_proof* pcs1, mlh_batched_pcs_proof* pcs2,
-                                    const ShiftProve* sh = nullptr) {
+                                    const ShiftProve* sh = nullptr,
+                                    const uint8_t* public_digest = nullptr) {
   const uint32_t L = com1->log_height, W = prog->p.width;
   TranscriptGuard guard(tr);
   SystemHead h(prog->p, L);
-  if (system_head(tr, prog->p, L, com1->root, com2 ? com2->root : nullptr, sum_column_mask, sum,
-                  column_sum, &h) != MLH_OK)
+  if (system_head(tr, prog->p, L, public_digest, com1->root, com2 ? com2->root : nullptr,
+                  sum_column_mask, sum, column_sum, &h) != MLH_OK)
     return fail(ctx, MLH_ERR_INVALID, "challenge set");
   PoolBuf delta(ctx);
   StreamDrain drain(sh ? ctx : nullptr);
@@ -1804,14 +1809,44 @@ mlh_status mlh_eq_table_rotate(mlh_ctx* ctx, const void* dev_in, uint32_t log_n,
   return MLH_OK;
 }
 
-mlh_status mlh_system_prove_shifted(mlh_ctx* ctx, const mlh_cs_program* prog,
-                                    const mlh_trace_commitment* com1,
-                                    const mlh_trace_commitment* com2, uint32_t sum_column_mask,
-                                    const uint32_t* shift_columns, uint32_t n_shifts,
-                                    const void* dev_matrix, const uint8_t sum[16],
-                                    const uint8_t column_sum[16], mlh_transcript* tr,
-                                    mlh_shifted_proof* proof) {
-  const uint32_t K = n_shifts;
+// ---- public columns (trace_public.hip; mlhip.h gives the format and the protocol) ----
+mlh_status mlh_trace_fill_public(mlh_ctx* ctx, const mlh_public_columns* spec, void* dev_matrix,
+                                 uint32_t log_height, uint32_t width) {
+  if (!ctx || !spec || !dev_matrix) return fail(ctx, MLH_ERR_INVALID, "null argument");
+  const PublicColumns& s = spec->p;
+  if (width < 1 || width > kTpMaxWidth || s.count() > width || log_height > kCsMaxLogHeight)
+    return fail(ctx, MLH_ERR_INVALID, "width 1..32, at most width public columns, log_height 0..32");
+  if (!s.fits(log_height))
+    return fail(ctx, MLH_ERR_INVALID, "a period or a sparse row of the spec is beyond the height");
+  PoolBuf img(ctx);
+  MLH_TRY(img.alloc(s.image.size()));
+  HIP_TRY(ctx, hipMemcpyAsync(img.p, s.image.data(), s.image.size(), hipMemcpyHostToDevice,
+                              ctx->stream));
+  ProfScope ps(ctx, "trace_fill_public");
+  HIP_TRY(ctx, launch_trace_fill_public(reinterpret_cast<fe*>(dev_matrix), img.p, s.count(),
+                                        s.sparse_off, s.n_sparse, log_height, width, ctx->stream));
+  ps.end();
+  return MLH_OK;  // (the image goes back to the pool: its next user is behind these launches on the stream)
+}
+
+mlh_status mlh_trace_fill_public_launch_info(uint32_t log_height, uint32_t width, uint32_t n_public,
+                                             uint32_t* tile_rows, uint32_t* blocks) {
+  if (!tile_rows || !blocks || width < 1 || width > kTpMaxWidth || n_public < 1 ||
+      n_public > kPcMaxColumns || n_public > width || log_height > kCsMaxLogHeight)
+    return MLH_ERR_INVALID;
+  *tile_rows = 1u << tp_log_rows(log_height, n_public);
+  *blocks = tp_blocks(log_height, n_public);
+  return MLH_OK;
+}
+
+mlh_status mlh_system_prove_public(mlh_ctx* ctx, const mlh_cs_program* prog,
+                                   const mlh_trace_commitment* com1,
+                                   const mlh_trace_commitment* com2, uint32_t sum_column_mask,
+                                   const uint32_t* shift_columns, uint32_t n_shifts,
+                                   const mlh_public_columns* spec, const void* dev_matrix,
+                                   const uint8_t sum[16], const uint8_t column_sum[16],
+                                   mlh_transcript* tr, mlh_shifted_proof* proof) {
+  const uint32_t K = n_shifts, F = spec ? spec->p.count() : 0;
   if (!ctx || !prog || !com1 || !dev_matrix || !sum || !column_sum || !tr || !proof ||
       !proof->sumcheck_polys || !proof->output ||
       (K && (!shift_columns || !proof->shift_polys || !proof->output2)))
@@ -1823,10 +1858,14 @@ mlh_status mlh_system_prove_shifted(mlh_ctx* ctx, const mlh_cs_program* prog,
     return fail(ctx, MLH_ERR_INVALID,
                 "shift list: distinct source columns below W, W + K the program's width, at most 32");
   const uint32_t W = Wx - K, L = com1->log_height;
-  if (P1 < 1 || P1 + P2 != W || (com2 && com2->log_height != L))
+  if (F >= W) return fail(ctx, MLH_ERR_INVALID, "as many public columns as the trace has columns");
+  if (P1 < 1 || P1 + P2 + F != W || (com2 && com2->log_height != L))
     return fail(ctx, MLH_ERR_INVALID,
-                "the commitments' widths and n_shifts must add up to the program's width (com2 "
-                "null iff all columns are pre-random), over the same rows");
+                "the commitments' widths, the public columns and n_shifts must add up to the "
+                "program's width (com2 null iff all committed columns are pre-random), over the "
+                "same rows");
+  if (spec && !spec->p.fits(L))
+    return fail(ctx, MLH_ERR_INVALID, "a period or a sparse row of the spec is beyond the height");
   if (W < 32 && (sum_column_mask >> W))
     return fail(ctx, MLH_ERR_INVALID, "sum column at or above the trace's width");
   if (h_load(sum) >= kModulus || h_load(column_sum) >= kModulus)
@@ -1849,7 +1888,7 @@ mlh_status mlh_system_prove_shifted(mlh_ctx* ctx, const mlh_cs_program* prog,
   }
   MLH_TRY(system_prove_core(ctx, prog, com1, com2, sum_column_mask, ext.p, sum, column_sum, tr,
                             proof->sumcheck_polys, proof->output, &proof->pcs[0], &proof->pcs[1],
-                            &sh));
+                            &sh, spec ? spec->p.digest : nullptr));
   proof->log_height = L;
   proof->width = W;
   proof->degree = prog->p.degree;
@@ -1858,6 +1897,17 @@ mlh_status mlh_system_prove_shifted(mlh_ctx* ctx, const mlh_cs_program* prog,
   proof->n_shifts = K;
   for (uint32_t k = 0; k < 32; ++k) proof->shift_columns[k] = k < K ? shift_columns[k] : 0u;
   return MLH_OK;
+}
+
+mlh_status mlh_system_prove_shifted(mlh_ctx* ctx, const mlh_cs_program* prog,
+                                    const mlh_trace_commitment* com1,
+                                    const mlh_trace_commitment* com2, uint32_t sum_column_mask,
+                                    const uint32_t* shift_columns, uint32_t n_shifts,
+                                    const void* dev_matrix, const uint8_t sum[16],
+                                    const uint8_t column_sum[16], mlh_transcript* tr,
+                                    mlh_shifted_proof* proof) {
+  return mlh_system_prove_public(ctx, prog, com1, com2, sum_column_mask, shift_columns, n_shifts,
+                                 nullptr, dev_matrix, sum, column_sum, tr, proof);
 }
 
 }  // extern "C"

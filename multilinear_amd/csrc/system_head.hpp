@@ -10,6 +10,7 @@
 #include "../../include/mlhip.h"
 #include "cs_program.hpp"
 #include "host_transcript.hpp"
+#include "public_columns.hpp"
 
 // Restores the caller's transcript to its state at construction unless keep()
 // was called: a failed prove or verify leaves it untouched (mlhip.h), the root
@@ -40,17 +41,18 @@ struct SystemHead {
       : row(16ull * log_height), randoms(16ull * P.n_randoms), mask(16ull * P.n_constraints) {}
 };
 
-// 1. absorb root1; 2. the trace randoms; 3. absorb root2 (null: one phase);
+// 0. with public columns (public_digest non-null), absorb the spec's 32-byte
+// digest; 1. absorb root1; 2. the trace randoms; 3. absorb root2 (null: one phase);
 // 4. the row and constraint challenges and the mask (mlh_system_challenges);
 // 5. with sum columns (sum_column_mask != 0; column_sum required), absorb
 // LE16(column_sum) and draw beta; claim = sum + beta * column_sum, else sum.
-// With root2 null and no sum columns this is the one-phase order byte for
+// With no public columns, root2 null and no sum columns this is the one-phase order byte for
 // byte: next_challenge() leaves the state as it was, so step 2's value is the
 // one step 4 draws.  out: a SystemHead(P, log_height).  The caller guards the
 // transcript.
 mlh_status system_head(mlh_transcript* tr, const CsProgram& P, uint32_t log_height,
-                       const uint8_t root1[32], const uint8_t* root2, uint32_t sum_column_mask,
-                       const uint8_t sum[16], const uint8_t* column_sum, SystemHead* out);
+                       const uint8_t* public_digest, const uint8_t root1[32], const uint8_t* root2,
+                       uint32_t sum_column_mask, const uint8_t sum[16], const uint8_t* column_sum, SystemHead* out);
 
 // The shift list of a shifted system over a program of width wext = W + K: K
 // distinct source columns below W (K = 0: no list).  Prover and verifier refuse

@@ -549,11 +549,12 @@ mlh_status mlh_system_trace_randoms(const mlh_transcript* tr, const uint8_t root
 // The transcript head of every system proof (system_head.hpp; the order is
 // mlhip.h's): the one place where the provers and the verifiers derive it.
 mlh_status mlh::system_head(mlh_transcript* tr, const CsProgram& P, uint32_t log_height,
-                            const uint8_t root1[32], const uint8_t* root2, uint32_t sum_column_mask,
-                            const uint8_t sum[16], const uint8_t* column_sum, SystemHead* out) {
+                            const uint8_t* public_digest, const uint8_t root1[32],
+                            const uint8_t* root2, uint32_t sum_column_mask, const uint8_t sum[16], const uint8_t* column_sum, SystemHead* out) {
   if (!tr || !root1 || !sum || !out || (sum_column_mask && !column_sum)) return MLH_ERR_INVALID;
   std::vector<uint8_t> cons(16ull * cs_log_nc(P.n_constraints));
-  mlh_transcript_absorb(tr, root1, 32);  // 1.
+  if (public_digest) mlh_transcript_absorb(tr, public_digest, 32);  // 0.
+  mlh_transcript_absorb(tr, root1, 32);                             // 1.
   uint8_t c[16];
   mlh_transcript_next_challenge(tr, c);  // 2. vec![next_challenge(); n] (system.rs:139)
   for (uint32_t i = 0; i < P.n_randoms; ++i) memcpy(out->randoms.data() + 16ull * i, c, 16);
@@ -677,22 +678,39 @@ struct ShiftVerify {
 // columns, pcs2 (null: one phase) for the rest -- and, with sh, those of the
 // same columns at rs'.  Every rejection is MLH_ERR_VERIFY with the transcript
 // as at entry.
+// pub (null: none; the caller has checked that it fits L and the width): the
+// last pub->p.count() of the W real columns are public -- its digest is
+// absorbed first, the openings cover the columns below them, and output (and,
+// with sh, output2) must hold the spec's own evaluations there (mlhip.h,
+// public columns).
 static mlh_status system_verify_core(const mlh_cs_program* prog, uint32_t L, uint32_t sum_column_mask,
                                      const uint8_t sum[16], const uint8_t* column_sum,
                                      const uint8_t* polys, const uint8_t* output,
                                      const mlh_batched_pcs_proof* pcs1,
                                      const mlh_batched_pcs_proof* pcs2, mlh_transcript* tr,
-                                     const ShiftVerify* sh = nullptr) {
+                                     const ShiftVerify* sh = nullptr,
+                                     const mlh_public_columns* pub = nullptr) {
   TranscriptGuard guard(tr);
   SystemHead h(prog->p, L);
   std::vector<u128> rs, rs2;
-  mlh_status st = system_head(tr, prog->p, L, pcs1->fri.batch_commitment,
+  mlh_status st = system_head(tr, prog->p, L, pub ? pub->p.digest : nullptr,
+                              pcs1->fri.batch_commitment,
                               pcs2 ? pcs2->fri.batch_commitment : nullptr, sum_column_mask, sum,
                               column_sum, &h);
   if (st == MLH_OK)
     st = cs_sumcheck_verify_rs(prog, L, h.row.data(), h.randoms.data(), h.mask.data(),
                                sum_column_mask, h.beta, h.claim, polys, output, tr, &rs);
   const uint32_t P1 = pcs1->fri.num_codes;
+  // the public columns' evaluations at `at` against the proof's, element for element
+  const auto public_ok = [&](const std::vector<u128>& at, const uint8_t* out) {
+    const uint32_t F = pub->p.count(), W = prog->p.width - (sh ? sh->K : 0);
+    std::vector<u128> want(F);
+    pc_evaluate(pub->p, L, at.data(), want.data());
+    for (uint32_t j = 0; j < F; ++j)
+      if (h_load(out + 16ull * (W - F + j)) != want[j]) return false;
+    return true;
+  };
+  if (st == MLH_OK && pub && !public_ok(rs, output)) st = MLH_ERR_VERIFY;
   if (st == MLH_OK && sh) {
     const uint32_t W = prog->p.width - sh->K;
     mlh_cs_program sp;
@@ -703,6 +721,7 @@ static mlh_status system_verify_core(const mlh_cs_program* prog, uint32_t L, uin
     shift_challenge(tr, output, W, sh->K, &lambdas, claim2);
     st = cs_sumcheck_verify_rs(&sp, L, nullptr, lambdas.data(), one, 0, nullptr, claim2, sh->polys,
                                sh->output2, tr, &rs2, succ_at, &rs);
+    if (st == MLH_OK && pub && !public_ok(rs2, sh->output2)) st = MLH_ERR_VERIFY;
   }
   std::vector<uint8_t> in(16ull * L);
   const auto open = [&](const std::vector<u128>& at, const uint8_t* out,
@@ -782,39 +801,79 @@ mlh_status mlh_shift_succ_evaluate(const uint8_t* x, const uint8_t* y, uint32_t 
   return MLH_OK;
 }
 
-mlh_status mlh_system_verify_shifted(const mlh_cs_program* prog, uint32_t log_height,
-                                     uint32_t pre_random_columns, uint32_t sum_column_mask,
-                                     const uint32_t* shift_columns, uint32_t n_shifts,
-                                     const uint8_t sum[16], const uint8_t column_sum[16],
-                                     const mlh_shifted_proof* proof, mlh_transcript* tr) {
-  const uint32_t K = n_shifts;
+// ---- public columns (public_columns.hpp; mlhip.h gives the format and the protocol) ----
+mlh_status mlh_public_columns_create(const uint8_t* wire, uint64_t len, mlh_public_columns** out) {
+  if (!wire || !out) return MLH_ERR_INVALID;
+  std::unique_ptr<mlh_public_columns> s(new mlh_public_columns());
+  if (!pc_decode(wire, len, s->p)) return MLH_ERR_INVALID;
+  *out = s.release();
+  return MLH_OK;
+}
+void mlh_public_columns_destroy(mlh_public_columns* spec) { delete spec; }
+uint32_t mlh_public_columns_count(const mlh_public_columns* spec) {
+  return spec ? spec->p.count() : 0;
+}
+mlh_status mlh_public_columns_digest(const mlh_public_columns* spec, uint8_t out[32]) {
+  if (!spec || !out) return MLH_ERR_INVALID;
+  memcpy(out, spec->p.digest, 32);
+  return MLH_OK;
+}
+mlh_status mlh_public_columns_evaluate(const mlh_public_columns* spec, uint32_t log_height,
+                                       const uint8_t* point, uint8_t* out) {
+  if (!spec || !out || (log_height && !point) || !spec->p.fits(log_height)) return MLH_ERR_INVALID;
+  std::vector<u128> x, v(spec->p.count());
+  if (!load_canonical(point, log_height, x)) return MLH_ERR_INVALID;
+  pc_evaluate(spec->p, log_height, x.data(), v.data());
+  for (uint32_t j = 0; j < spec->p.count(); ++j) h_store(out + 16ull * j, v[j]);
+  return MLH_OK;
+}
+
+mlh_status mlh_system_verify_public(const mlh_cs_program* prog, uint32_t log_height,
+                                    uint32_t pre_random_columns, uint32_t sum_column_mask,
+                                    const uint32_t* shift_columns, uint32_t n_shifts,
+                                    const mlh_public_columns* spec, const uint8_t sum[16],
+                                    const uint8_t column_sum[16], const mlh_shifted_proof* proof,
+                                    mlh_transcript* tr) {
+  const uint32_t K = n_shifts, F = spec ? spec->p.count() : 0;
   if (!prog || !sum || !column_sum || !proof || !tr || !proof->sumcheck_polys || !proof->output ||
       !proof->pcs[0].sumcheck_polys || (K && !shift_columns) ||
-      !shift_list_ok(prog->p.width, shift_columns, K))
+      !shift_list_ok(prog->p.width, shift_columns, K) || F >= prog->p.width - K ||
+      (spec && !spec->p.fits(log_height)))
     return MLH_ERR_INVALID;
   const CsProgram& P = prog->p;
-  const uint32_t L = log_height, W = P.width - K, P1 = pre_random_columns;
-  const bool two = P1 < W;
-  if (L < 1 || L > kCsMaxLogHeight || P1 < 1 || P1 > W || (W < 32 && (sum_column_mask >> W)) ||
+  const uint32_t L = log_height, W = P.width - K, C = W - F, P1 = pre_random_columns;
+  const bool two = P1 < C;  // C: the committed columns
+  if (L < 1 || L > kCsMaxLogHeight || P1 < 1 || P1 > C || (W < 32 && (sum_column_mask >> W)) ||
       proof->log_height != L || proof->width != W || proof->degree != P.degree ||
       proof->pre_random_columns != P1 || proof->sum_column_mask != sum_column_mask ||
       proof->n_shifts != K || proof->pcs[0].fri.num_codes != P1 ||
-      (two && (!proof->pcs[1].sumcheck_polys || proof->pcs[1].fri.num_codes != W - P1)) ||
+      (two && (!proof->pcs[1].sumcheck_polys || proof->pcs[1].fri.num_codes != C - P1)) ||
       h_load(sum) >= kModulus || h_load(column_sum) >= kModulus)
     return MLH_ERR_VERIFY;
   for (uint32_t k = 0; k < 32; ++k)
     if (proof->shift_columns[k] != (k < K ? shift_columns[k] : 0u)) return MLH_ERR_VERIFY;
   if (!K)
     return system_verify_core(prog, L, sum_column_mask, sum, column_sum, proof->sumcheck_polys,
-                              proof->output, &proof->pcs[0], two ? &proof->pcs[1] : nullptr, tr);
+                              proof->output, &proof->pcs[0], two ? &proof->pcs[1] : nullptr, tr,
+                              nullptr, spec);
   if (!proof->shift_polys || !proof->output2 || !proof->pcs_shift[0].sumcheck_polys ||
       proof->pcs_shift[0].fri.num_codes != P1 ||
-      (two && (!proof->pcs_shift[1].sumcheck_polys || proof->pcs_shift[1].fri.num_codes != W - P1)))
+      (two && (!proof->pcs_shift[1].sumcheck_polys || proof->pcs_shift[1].fri.num_codes != C - P1)))
     return MLH_ERR_VERIFY;
   const ShiftVerify sh = {shift_columns, K, proof->shift_polys, proof->output2, &proof->pcs_shift[0],
                           two ? &proof->pcs_shift[1] : nullptr};
   return system_verify_core(prog, L, sum_column_mask, sum, column_sum, proof->sumcheck_polys,
-                            proof->output, &proof->pcs[0], two ? &proof->pcs[1] : nullptr, tr, &sh);
+                            proof->output, &proof->pcs[0], two ? &proof->pcs[1] : nullptr, tr, &sh,
+                            spec);
+}
+
+mlh_status mlh_system_verify_shifted(const mlh_cs_program* prog, uint32_t log_height,
+                                     uint32_t pre_random_columns, uint32_t sum_column_mask,
+                                     const uint32_t* shift_columns, uint32_t n_shifts,
+                                     const uint8_t sum[16], const uint8_t column_sum[16],
+                                     const mlh_shifted_proof* proof, mlh_transcript* tr) {
+  return mlh_system_verify_public(prog, log_height, pre_random_columns, sum_column_mask,
+                                  shift_columns, n_shifts, nullptr, sum, column_sum, proof, tr);
 }
 
 }  // extern "C"
