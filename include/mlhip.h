@@ -85,7 +85,30 @@ mlh_status mlh_set_coop_spin_limit(mlh_ctx* ctx, uint32_t sleeps);
  * off the transcript chain for n_vars <= max_vars (default and cap 24) and
  * with one cooperative launch per round above it; both give the same proof. */
 mlh_status mlh_set_pcs_fused_max(mlh_ctx* ctx, uint32_t max_vars);
+/* Binds the context to another HIP stream.  Work the context enqueued before
+ * the switch is ordered before work it enqueues after it, on the device and
+ * without a host wait: the new stream waits for an event recorded on the old
+ * one.  So the caller need not synchronise around a switch -- the context's
+ * pooled scratch, its cached tables (which may still be being built) and a
+ * cache eviction's drain stay correct across it.  Passing the stream the
+ * context already has does nothing.  The stream being left must still exist
+ * (MLH_ERR_HIP otherwise; the context is bound to the new stream even then,
+ * but unordered).  Not promised: concurrent use of one
+ * context from two streams (or two threads); work the caller itself enqueues
+ * on either stream is ordered only by the caller.  Use one context per
+ * stream for independent work. */
 mlh_status mlh_set_stream(mlh_ctx* ctx, void* hip_stream);
+/* Test hook: while word != 0, every scratch buffer the library hands to its
+ * own kernels is first filled with `word` (as 32-bit words) on the context's
+ * stream: each block of the device memory pool when it is given out, each new
+ * cache table before its build kernel, the NTT ping-pong buffer when it is
+ * (re)allocated.  The call itself fills the context's fixed scratch (reduction
+ * partials, the 64-element scratch, the current NTT buffer) on the stream and,
+ * after synchronising the stream, the pinned staging buffers on the host.  A
+ * kernel that reads a scratch word it never wrote then computes with `word`
+ * instead of a stale, plausible value.  0 (the default) turns it off; off, it
+ * costs nothing. */
+mlh_status mlh_set_scratch_poison(mlh_ctx* ctx, uint32_t word);
 mlh_status mlh_synchronize(mlh_ctx* ctx);
 /* The message of ctx's last failure; with ctx == NULL, why this thread's last
  * mlh_context_create failed. */

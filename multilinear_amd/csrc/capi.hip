@@ -109,7 +109,7 @@ static mlh_status table_alloc(mlh_ctx* ctx, const TableKey& k, size_t bytes, fe*
   HIP_TRY(ctx, hipMalloc(d, bytes));
   ctx->tables[k] = CachedTable{*d, bytes, ++ctx->table_stamp};
   ctx->table_bytes += bytes;
-  return MLH_OK;
+  return poison_fill(ctx, *d, bytes);  // before the build kernel the caller enqueues
 }
 
 // table[t] = base^t * scale, t < count, cached per context.  expand: 4 fe per
@@ -258,6 +258,7 @@ static mlh_status ensure_ntt_scratch(mlh_ctx* ctx, uint32_t log_n) {
     }
     HIP_TRY(ctx, hipMalloc(&ctx->ntt_scratch, need));
     ctx->ntt_scratch_bytes = need;
+    MLH_TRY(poison_fill(ctx, ctx->ntt_scratch, need));
   }
   return MLH_OK;
 }
@@ -435,6 +436,17 @@ mlh_status mlh_context_create(int device, void* hip_stream, mlh_ctx** out) {
   }
   c->dev_status = reinterpret_cast<volatile uint32_t*>(st);
   *c->dev_status = 0;
+  // (created here, with the context's device current: mlh_set_stream may be
+  // called with another device current)
+  if (hipEventCreateWithFlags(&c->switch_ev, hipEventDisableTiming) != hipSuccess) {
+    snprintf(g_create_err, sizeof g_create_err, "mlh_context_create: hipEventCreate failed (%s)",
+             hipGetErrorString(hipGetLastError()));
+    (void)hipFree(c->partials);
+    (void)hipFree(c->small);
+    (void)hipHostFree(c->pinned);
+    (void)hipHostFree(st);
+    return MLH_ERR_HIP;
+  }
   *out = c.release();
   return MLH_OK;
 }
@@ -447,6 +459,7 @@ void mlh_context_destroy(mlh_ctx* ctx) {
   if (ctx->side2) (void)hipStreamSynchronize(ctx->side2);
   resolve_profile(ctx);
   for (auto e : ctx->ev_free) (void)hipEventDestroy(e);
+  if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
   for (auto& kv : ctx->tables) (void)hipFree(kv.second.d);
   for (auto& kv : ctx->pool) (void)hipFree(kv.second);
   for (auto& kv : ctx->live) (void)hipFree(kv.first);
@@ -493,7 +506,31 @@ mlh_status mlh_set_pcs_fused_max(mlh_ctx* ctx, uint32_t max_vars) {
 
 mlh_status mlh_set_stream(mlh_ctx* ctx, void* hip_stream) {
   if (!ctx) return MLH_ERR_INVALID;
-  ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
+  hipStream_t next = reinterpret_cast<hipStream_t>(hip_stream);
+  if (next == ctx->stream) return MLH_OK;
+  // Order the new stream behind the old one on the device (no host wait):
+  // pool blocks, cached tables still being built and an eviction's drain all
+  // assume that later work of the context runs after its earlier work.
+  hipStream_t prev = ctx->stream;
+  ctx->stream = next;
+  HIP_TRY(ctx, hipEventRecord(ctx->switch_ev, prev));
+  HIP_TRY(ctx, hipStreamWaitEvent(next, ctx->switch_ev, 0));
+  return MLH_OK;
+}
+
+mlh_status mlh_set_scratch_poison(mlh_ctx* ctx, uint32_t word) {
+  if (!ctx) return MLH_ERR_INVALID;
+  ctx->poison = word;
+  if (!word) return MLH_OK;
+  MLH_TRY(poison_fill(ctx, ctx->partials, 2 * kMaxRedBlocks * sizeof(fe)));
+  MLH_TRY(poison_fill(ctx, ctx->small, 64 * sizeof(fe)));
+  MLH_TRY(poison_fill(ctx, ctx->ntt_scratch, ctx->ntt_scratch_bytes));
+  // the pinned staging is filled by the host: wait for copies that still use it
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  uint32_t* w = reinterpret_cast<uint32_t*>(ctx->pinned);
+  for (size_t i = 0; i < kPinnedBytes / 4; ++i) w[i] = word;
+  w = reinterpret_cast<uint32_t*>(ctx->qstage);
+  for (size_t i = 0; i < ctx->qstage_bytes / 4; ++i) w[i] = word;
   return MLH_OK;
 }
 

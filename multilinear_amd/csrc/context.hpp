@@ -84,6 +84,11 @@ struct mlh_ctx {
   bool ntt_wide_offsets = false;
   uint32_t forced_plan[kMaxPasses] = {0};
   uint32_t forced_plan_len = 0;
+  // mlh_set_scratch_poison: nonzero -> every pool block, new cache table and
+  // NTT scratch buffer is filled with this word before its first use
+  uint32_t poison = 0;
+  // mlh_set_stream: recorded on the stream left, waited for on the one entered
+  hipEvent_t switch_ev = nullptr;
   // kernel timer (mlh_profile_*): HIP events on the launch stream
   bool prof_on = false;
   uint32_t prof_every = 1;  // bracket every prof_every-th transform / launch of each label
@@ -273,15 +278,26 @@ inline mlh::u128 from_fe(const mlh::fe& x) {
   return v;
 }
 
+// Scratch poison (mlh_set_scratch_poison): fill a buffer the library is about
+// to hand to its own kernels, on the context's stream.  Off: nothing.
+inline mlh_status poison_fill(mlh_ctx* ctx, void* p, size_t bytes) {
+  if (!ctx->poison || !p || bytes < 4) return MLH_OK;
+  if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)ctx->poison, bytes / 4,
+                        ctx->stream) != hipSuccess)
+    return fail(ctx, MLH_ERR_HIP, "scratch poison: hipMemsetD32Async failed");
+  return MLH_OK;
+}
+
 // pooled device allocation: large per-call buffers are reused across calls
 inline mlh_status pool_alloc(mlh_ctx* ctx, size_t bytes, void** out) {
   bytes = (bytes + 255) & ~(size_t)255;
   auto it = ctx->pool.lower_bound(bytes);
   if (it != ctx->pool.end() && it->first <= bytes + bytes / 4) {
     *out = it->second;
-    ctx->live[it->second] = it->first;
+    const size_t have = it->first;
+    ctx->live[it->second] = have;
     ctx->pool.erase(it);
-    return MLH_OK;
+    return poison_fill(ctx, *out, have);
   }
   void* p = nullptr;
   hipError_t e = hipMalloc(&p, bytes);
@@ -294,7 +310,7 @@ inline mlh_status pool_alloc(mlh_ctx* ctx, size_t bytes, void** out) {
   }
   ctx->live[p] = bytes;
   *out = p;
-  return MLH_OK;
+  return poison_fill(ctx, p, bytes);
 }
 inline void pool_free(mlh_ctx* ctx, void* p) {
   if (!p) return;
