@@ -1123,6 +1123,61 @@ mlh_status mlh_trace_fill_shaped(mlh_ctx* ctx, const mlh_fill_program* prog, voi
 mlh_status mlh_trace_column_sum(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
                                 uint32_t width, uint32_t column_mask, uint8_t out[16]);
 
+/* ---- running sums and running products on the device ------------------------ *
+ * The column that a next-row constraint next(z) = z * t or next(z) = z + t
+ * holds (the grand product of a permutation or multiset argument, a memory
+ * accumulator, the running sum of a log-derivative bus) is a prefix scan over
+ * the 2^log_height rows.  This call writes up to 8 of them in place, with no
+ * host copy of a column.
+ * For scan s let t[i] = matrix[i][src_columns[s]] as the matrix stood when the
+ * call began, o = + (MLH_SCAN_ADD) or * (MLH_SCAN_MUL) in the field and init_s =
+ * host_inits[16 s ..].  After the call, with H = 2^log_height,
+ *   z[0] = init_s,  z[i + 1] = z[i] o t[i],
+ *   matrix[i][dst_columns[s]] = z[i] for every i < H,
+ *   totals_out[16 s ..] = z[H - 1] o t[H - 1]:
+ * the exclusive scan, the column that first * (z - init) and next(z) - z o t
+ * constrain; the total is the value across the cyclic wrap, so next(z) = z o t
+ * holds on the last row without a (1 - last) gate exactly when total_s ==
+ * init_s (a grand product that closes to 1).  The inclusive form is one
+ * row-local fill on top (z o t, mlh_trace_fill); there is no flag for it.
+ * dst may equal src (in place), a destination may be the source of another
+ * scan (which still sees the old values), two scans may share a source;
+ * destination columns must be distinct, and the columns that are no
+ * destination are not written.
+ * width 1..32, log_height 0..32, n_scans 1..8, ops 0 or 1, columns below width,
+ * inits canonical.  Anything else and a NULL pointer (totals_out excepted) is
+ * MLH_ERR_INVALID before anything is enqueued: the matrix is untouched.
+ * Three launches on the context stream, none of which waits for another
+ * workgroup: the blocks' aggregates, their exclusive scan seeded with the
+ * inits (one block), and the scan of each block's rows behind its offset; one
+ * launch when there is one block.  The field operations are exact and
+ * associative: the bytes do not depend on the launch shape.  With totals_out
+ * == NULL the call does not wait for the device; otherwise it synchronises
+ * once to return the totals, as mlh_trace_column_sum does. */
+#define MLH_SCAN_ADD 0
+#define MLH_SCAN_MUL 1
+mlh_status mlh_trace_scan(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height, uint32_t width,
+                          uint32_t n_scans, const uint8_t* ops, const uint8_t* src_columns,
+                          const uint8_t* dst_columns, const uint8_t* host_inits /* n_scans x 16 */,
+                          uint8_t* totals_out /* n_scans x 16, or NULL */);
+/* Its launch shape: threads per block (256), consecutive rows per thread (4)
+ * and blocks (min(ceil(2^log_height / (threads * rows_per_thread)), 1024)); a
+ * block takes ceil(tiles / blocks) consecutive tiles of threads *
+ * rows_per_thread rows, the last blocks fewer or none.  The limits of
+ * mlh_trace_scan. */
+mlh_status mlh_trace_scan_launch_info(uint32_t log_height, uint32_t width, uint32_t n_scans,
+                                      uint32_t* threads, uint32_t* rows_per_thread,
+                                      uint32_t* blocks);
+/* The same kernels and the same bytes under another shape, for tests of the
+ * seams at small heights and for measurements: threads 64, 128 or 256,
+ * rows_per_thread a power of two up to 16, max_blocks 1..1024 (the grid is
+ * min(tiles, max_blocks) blocks); MLH_ERR_INVALID otherwise. */
+mlh_status mlh_trace_scan_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                 uint32_t width, uint32_t n_scans, const uint8_t* ops,
+                                 const uint8_t* src_columns, const uint8_t* dst_columns,
+                                 const uint8_t* host_inits, uint8_t* totals_out, uint32_t threads,
+                                 uint32_t rows_per_thread, uint32_t max_blocks);
+
 /* ---- a lookup's multiplicities on the device -------------------------------- *
  * The multiplicity column m of a log-derivative lookup (v = -m / (gamma - t))
  * is a pre-random column: it must stand in the matrix before

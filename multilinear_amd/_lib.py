@@ -306,6 +306,10 @@ SIGNATURES = {
                                         ctypes.POINTER(_U32)]),
     "mlh_trace_fill_shaped": (_I, [_P, _P, _P, _U32, _U32, _P, _U32, _U32]),
     "mlh_trace_column_sum": (_I, [_P, _P, _U32, _U32, _U32, _P]),
+    "mlh_trace_scan": (_I, [_P, _P, _U32, _U32, _U32, _P, _P, _P, _P, _P]),
+    "mlh_trace_scan_launch_info": (_I, [_U32, _U32, _U32, ctypes.POINTER(_U32),
+                                        ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "mlh_trace_scan_shaped": (_I, [_P, _P, _U32, _U32, _U32, _P, _P, _P, _P, _P, _U32, _U32, _U32]),
     "mlh_trace_lookup_counts": (_I, [_P, _P, _U32, _U32, _U32, _U32, _U32, ctypes.POINTER(_U64),
                                      ctypes.POINTER(_U64)]),
     "mlh_trace_lookup_counts_launch_info": (_I, [_U32, _U32, ctypes.POINTER(_U32),

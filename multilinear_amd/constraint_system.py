@@ -32,7 +32,10 @@ counted in place before ``phased_prover`` by ``Trace.lookup_multiplicities``
 (mlh_trace_lookup_counts), or, for keys of several columns such as (x, y, x ^ y),
 by ``Trace.lookup_tuple_multiplicities`` (mlh_trace_lookup_tuple_counts);
 ``tuple_key`` spells the compressed key of such a lookup for the fill and the
-constraint.
+constraint.  The column a next-row constraint ``nxt(z) - z * t`` or ``nxt(z) -
+z - t`` holds (a grand product, a running sum) is written in phase 2 by
+``PhasedProver.scan`` / ``Trace.scan`` (mlh_trace_scan), which also return the
+total across the cyclic wrap.
 """
 import ctypes
 import struct
@@ -543,6 +546,23 @@ class Trace:
                                           self._height.bit_length() - 1, self._width), ctx)
         return spec
 
+    def scan(self, scans, device=0, totals=True):
+        """Running sums and running products down columns, in place
+        (mlh_trace_scan).  ``scans``: a list of (op, src, dst, init), op "add"
+        or "mul": column dst becomes z with z[0] = init and z[i + 1] = z[i] op
+        t[i], t the column src as it stood at the call.  Returns the list of
+        totals z[height - 1] op t[height - 1], or None when ``totals`` is false
+        (the call then does not wait for the device)."""
+        ops, src, dst, inits = _scan_arrays(scans, self._width)
+        n = len(ops)
+        out = (ctypes.c_uint8 * (16 * n))() if totals else None
+        ctx = context(device)
+        check(lib().mlh_trace_scan(ctx, ptr(self._matrix), self._height.bit_length() - 1,
+                                   self._width, n, (ctypes.c_uint8 * n)(*ops),
+                                   (ctypes.c_uint8 * n)(*src), (ctypes.c_uint8 * n)(*dst),
+                                   _elems(inits), out), ctx)
+        return _split(out, n) if totals else None
+
     def extend_next(self, shift_columns, device=0):
         """The extension of a shifted system (mlh_trace_extend_next): a new
         Trace of width + len(shift_columns) columns whose column width + k is
@@ -710,6 +730,39 @@ def lookup_counts_launch_info(log_height, n_value_columns):
     check(lib().mlh_trace_lookup_counts_launch_info(log_height, n_value_columns, ctypes.byref(t),
                                                     ctypes.byref(b), ctypes.byref(s)))
     return t.value, b.value, s.value
+
+
+SCAN_OPS = {"add": 0, "mul": 1}
+
+
+def _scan_arrays(scans, width):
+    """(ops, sources, destinations, inits) of a list of (op, src, dst, init),
+    checked as mlh_trace_scan checks them."""
+    scans = list(scans)
+    if not 1 <= len(scans) <= 8:
+        raise ValueError("1 to 8 scans in one call, not %d" % len(scans))
+    ops, src, dst, inits = [], [], [], []
+    for op, s, d, init in scans:
+        if op not in SCAN_OPS:
+            raise ValueError("scan op %r is neither 'add' nor 'mul'" % (op,))
+        for name, j in (("source", s), ("destination", d)):
+            if not 0 <= j < width:
+                raise ValueError("%s column %r outside the trace" % (name, j))
+        if d in dst:
+            raise ValueError("two scans write column %d" % d)
+        ops.append(SCAN_OPS[op])
+        src.append(s)
+        dst.append(d)
+        inits.append(init)
+    return ops, src, dst, inits
+
+
+def trace_scan_launch_info(log_height, width, n_scans):
+    """(threads per block, consecutive rows per thread, blocks) of mlh_trace_scan."""
+    t, k, b = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    check(lib().mlh_trace_scan_launch_info(log_height, width, n_scans, ctypes.byref(t),
+                                           ctypes.byref(k), ctypes.byref(b)))
+    return t.value, k.value, b.value
 
 
 def trace_column_sum(dev_matrix, width, columns, device=0):
@@ -1058,6 +1111,21 @@ class PhasedProver:
             raise ValueError("fill writes a column below pre_random_columns (%d), which "
                              "commitment 1 already holds" % lay.pre_random_columns)
         return self._trace.fill(prog, self.randoms, self._device)
+
+    def scan(self, scans):
+        """``Trace.scan`` on the prover's trace: running sums and products
+        into columns at and above pre_random_columns and below the public
+        strip; returns the totals.  A destination that commitment 1 already
+        holds, or a public column (which the verifier derives): ValueError."""
+        lay = self._layout
+        scans = list(scans)
+        for _, _, d, _ in scans:
+            if 0 <= d < lay.pre_random_columns:
+                raise ValueError("scan writes column %d below pre_random_columns (%d), which "
+                                 "commitment 1 already holds" % (d, lay.pre_random_columns))
+            if self._committed <= d < lay.columns:
+                raise ValueError("scan writes the public column %d" % d)
+        return self._trace.scan(scans, self._device)
 
     def prove(self, transcript, total_sum, column_sum=None):
         """mlh_system_prove_phased on a clone of the trace's matrix.

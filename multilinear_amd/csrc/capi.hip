@@ -3,7 +3,7 @@
 //
 // Here: the context, the pool and the twiddle-table cache, the NTT /
 // Reed-Solomon / Merkle / field entries, the stepwise sumcheck entries, the
-// trace commitment, the phase-2 fill and column sum, the constraint-system
+// trace commitment, the phase-2 fill, column sum and column scans, the constraint-system
 // sumcheck and the system proofs.
 // The FRI prover is fri_prover.hip; the sumcheck, PCS and batched-PCS provers
 // above it, pcs_prover.hip; the multi-GPU schedules, sharded.hip, and their
@@ -50,6 +50,7 @@
 #include "trace_fill.hpp"
 #include "trace_lookup.hpp"
 #include "trace_public.hpp"
+#include "trace_scan.hpp"
 #include "trace_shift.hpp"
 #include "transcript_dev.hpp"
 
@@ -1282,6 +1283,84 @@ mlh_status mlh_trace_column_sum(mlh_ctx* ctx, const void* dev_matrix, uint32_t l
   HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, ctx->small, 16, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   memcpy(out, ctx->pinned, 16);
+  return MLH_OK;
+}
+
+// ---- running sums and running products down columns (trace_scan.hip) ----
+
+static_assert(MLH_SCAN_ADD == kScanAdd && MLH_SCAN_MUL == kScanMul, "mlhip.h and trace_scan.hpp agree");
+
+static bool scan_dims_ok(uint32_t log_height, uint32_t width, uint32_t n_scans) {
+  return log_height <= kCsMaxLogHeight && width >= 1 && width <= kCsMaxWidth && n_scans >= 1 &&
+         n_scans <= kScanMaxScans;
+}
+
+mlh_status mlh_trace_scan_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                 uint32_t width, uint32_t n_scans, const uint8_t* ops,
+                                 const uint8_t* src_columns, const uint8_t* dst_columns,
+                                 const uint8_t* host_inits, uint8_t* totals_out, uint32_t threads,
+                                 uint32_t rows_per_thread, uint32_t max_blocks) {
+  if (!ctx || !dev_matrix || !ops || !src_columns || !dst_columns || !host_inits ||
+      !scan_dims_ok(log_height, width, n_scans) ||
+      !scan_shape_ok(threads, rows_per_thread, max_blocks))
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_scan: bad argument");
+  ScanArgs a{};
+  uint32_t written = 0;
+  for (uint32_t s = 0; s < n_scans; ++s) {
+    if (ops[s] > kScanMul || src_columns[s] >= width || dst_columns[s] >= width ||
+        ((written >> dst_columns[s]) & 1u))
+      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_scan: bad op, column out of range or "
+                                        "destination written twice");
+    written |= 1u << dst_columns[s];
+    const u128 init = h_load(host_inits + 16ull * s);
+    if (init >= kModulus) return fail(ctx, MLH_ERR_INVALID, "mlh_trace_scan: non-canonical init");
+    a.op[s] = ops[s];
+    a.src[s] = src_columns[s];
+    a.dst[s] = dst_columns[s];
+    a.init[s] = to_fe(init);
+  }
+  a.m = reinterpret_cast<fe*>(dev_matrix);
+  a.height = 1ull << log_height;
+  a.width = width;
+  a.n_scans = n_scans;
+  a.rows_per_thread = rows_per_thread;
+  a.tiles = scan_tiles(a.height, threads, rows_per_thread);
+  a.blocks = scan_blocks(a.tiles, max_blocks);
+  a.tiles_per_block = (a.tiles + a.blocks - 1) / a.blocks;
+  PoolBuf scratch(ctx);  // the blocks' aggregates and offsets, the totals
+  MLH_TRY(scratch.alloc(scan_scratch_elems(n_scans, a.blocks) * sizeof(fe)));
+  a.aggregates = scratch.as<fe>();
+  a.offsets = a.aggregates + (size_t)n_scans * a.blocks;
+  a.totals = a.offsets + (size_t)n_scans * a.blocks;
+  ProfScope ps(ctx, "trace_scan");
+  HIP_TRY(ctx, launch_trace_scan(a, threads, ctx->stream));
+  ps.end();
+  if (!totals_out) return MLH_OK;  // (the scratch's next user is behind these launches)
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, a.totals, 16ull * n_scans, hipMemcpyDeviceToHost,
+                              ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(totals_out, ctx->pinned, 16ull * n_scans);
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_scan(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height, uint32_t width,
+                          uint32_t n_scans, const uint8_t* ops, const uint8_t* src_columns,
+                          const uint8_t* dst_columns, const uint8_t* host_inits,
+                          uint8_t* totals_out) {
+  return mlh_trace_scan_shaped(ctx, dev_matrix, log_height, width, n_scans, ops, src_columns,
+                               dst_columns, host_inits, totals_out, kScanThreads,
+                               kScanRowsPerThread, kScanMaxBlocks);
+}
+
+mlh_status mlh_trace_scan_launch_info(uint32_t log_height, uint32_t width, uint32_t n_scans,
+                                      uint32_t* threads, uint32_t* rows_per_thread,
+                                      uint32_t* blocks) {
+  if (!threads || !rows_per_thread || !blocks || !scan_dims_ok(log_height, width, n_scans))
+    return MLH_ERR_INVALID;
+  *threads = kScanThreads;
+  *rows_per_thread = kScanRowsPerThread;
+  *blocks = scan_blocks(scan_tiles(1ull << log_height, kScanThreads, kScanRowsPerThread),
+                        kScanMaxBlocks);
   return MLH_OK;
 }
 
