@@ -1024,7 +1024,9 @@ mlh_status mlh_trace_fill_public_launch_info(uint32_t log_height, uint32_t width
  *
  * The prover does not check that the strip of dev_matrix (see
  * mlh_trace_fill_public) equals the spec: like a broken constraint, a wrong
- * strip returns MLH_OK and the verifier rejects.  MLH_ERR_INVALID, with the
+ * strip returns MLH_OK and the verifier rejects (mlh_trace_check and
+ * mlh_trace_check_public say beforehand which constraint, which column and
+ * which row).  MLH_ERR_INVALID, with the
  * transcript as at entry, for every argument error of the shifted call and for
  * F >= W, widths that do not add up (a commitment2 given although P = W - F
  * included) and a spec that does not fit the height. */
@@ -1177,6 +1179,96 @@ mlh_status mlh_trace_scan_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_he
                                  const uint8_t* src_columns, const uint8_t* dst_columns,
                                  const uint8_t* host_inits, uint8_t* totals_out, uint32_t threads,
                                  uint32_t rows_per_thread, uint32_t max_blocks);
+
+/* ---- the witness check on the device ---------------------------------------- *
+ * The provers do not detect a trace that breaks a constraint or a public strip
+ * that differs from its spec: they return MLH_OK and the verifier rejects.
+ * These calls tell the caller beforehand which constraint fails, on how many
+ * rows and where first, with no host copy of the trace.
+ *
+ * mlh_trace_check runs every constraint of `prog` (constraints.rs:3-10: an
+ * expression of the row and the randoms that must be zero) on every row, each
+ * on its own and without the constraint mask of evaluation.rs:21-29.  With H =
+ * 2^log_height, W = width and K = n_shifts source columns, as
+ * mlh_system_prove_shifted takes them, the program is W + K wide; on row i its
+ * column operand j < W is matrix[i][j] and column operand W + k is
+ * matrix[(i + 1) mod H][shift_columns[k]].  No extension is materialised.
+ * Constraint c fails on row i when its output there is not the field's zero.
+ *   counts_out[c]     = the number of rows on which c fails;
+ *   first_rows_out[c] = the lowest such row, UINT64_MAX when there is none;
+ *   report            = as commented in the struct.
+ * The constraint mask and the delta table play no part, so the check can run
+ * before any commitment exists (the randoms are whatever the caller will
+ * prove with).  The matrix is not written.  The result is a pure function of
+ * the matrix, the program, the randoms and the shift list: it does not depend
+ * on the launch shape or on the order of the atomics (only integer adds and
+ * mins cross lanes).
+ * width 1..32, width + n_shifts equal to the program's width and at most 32,
+ * log_height 0..32 (one row is its own next row, as in mlh_trace_extend_next);
+ * source columns below width, duplicates allowed here as in
+ * mlh_trace_extend_next; randoms canonical, host_randoms may be NULL when the
+ * program has none.  Anything else and a NULL ctx, prog, dev_matrix or report
+ * is MLH_ERR_INVALID: nothing is enqueued and the outputs stay untouched.  A
+ * failing trace is MLH_OK.
+ * One launch: a block takes chunks of `threads` consecutive rows, loads them
+ * coalesced into LDS (width + n_shifts + temps slots of 16 bytes per lane),
+ * takes the next row's operands from the neighbouring lane -- the chunk's last
+ * lane from global memory, across the cyclic wrap behind the last row --
+ * interprets the program once per row and reduces the verdicts with wave
+ * ballots, per-block LDS counters and 64-bit atomics into a pooled array that
+ * the call zeroes on the stream first.  No workgroup waits for another.
+ * Synchronises once to return the counters, as mlh_trace_lookup_counts does. */
+typedef struct mlh_trace_check_report {
+  uint64_t n_bad_rows;           /* rows on which at least one constraint is nonzero */
+  uint64_t first_bad_row;        /* the lowest of them; UINT64_MAX when none         */
+  uint32_t first_bad_constraint; /* the lowest constraint that is nonzero on that row;
+                                    UINT32_MAX when none                             */
+  uint32_t reserved;             /* 0 */
+} mlh_trace_check_report;
+mlh_status mlh_trace_check(mlh_ctx* ctx, const mlh_cs_program* prog, const void* dev_matrix,
+                           uint32_t log_height, uint32_t width,
+                           const uint32_t* shift_columns, uint32_t n_shifts,
+                           const uint8_t* host_randoms,
+                           uint64_t* counts_out /* [n_constraints] or NULL */,
+                           uint64_t* first_rows_out /* [n_constraints] or NULL */,
+                           mlh_trace_check_report* report);
+/* Its launch shape: threads per block (the largest of 256, 128, 64 whose
+ * program width + n_temps LDS slots of 16 bytes fit 152 KiB) and blocks
+ * (min(ceil(2^log_height / (threads * 4)), 1024), each looping over chunks of
+ * `threads` rows with the grid's stride).  log_height 0..32. */
+mlh_status mlh_trace_check_launch_info(const mlh_cs_program* prog, uint32_t log_height,
+                                       uint32_t* threads, uint32_t* blocks);
+/* The same kernel and the same counters under another shape, for tests of the
+ * seams at small heights and for measurements: threads 64, 128 or 256,
+ * max_blocks 1..1024 (the grid is min(ceil(2^log_height / threads),
+ * max_blocks) blocks); MLH_ERR_INVALID otherwise and when the slots do not fit
+ * 152 KiB of LDS at that block size. */
+mlh_status mlh_trace_check_shaped(mlh_ctx* ctx, const mlh_cs_program* prog, const void* dev_matrix,
+                                  uint32_t log_height, uint32_t width,
+                                  const uint32_t* shift_columns, uint32_t n_shifts,
+                                  const uint8_t* host_randoms, uint64_t* counts_out,
+                                  uint64_t* first_rows_out, mlh_trace_check_report* report,
+                                  uint32_t threads, uint32_t max_blocks);
+/* The public strip against its spec.  With F the spec's columns,
+ *   counts_out[j]     = the number of rows i where matrix[i][width - F + j]
+ *                       differs in its 16 bytes from what mlh_trace_fill_public
+ *                       would write there;
+ *   first_rows_out[j] = the lowest such row, UINT64_MAX when there is none;
+ *   *n_bad_rows       = the rows with a difference in any of the F columns,
+ *   *first_bad_row    = the lowest of them, UINT64_MAX when there is none.
+ * counts_out and first_rows_out ([F]) may be NULL.  The limits and argument
+ * errors of mlh_trace_fill_public, and MLH_ERR_INVALID for a NULL n_bad_rows
+ * or first_bad_row; no byte of the matrix is written, and a committed column
+ * is not looked at.  The tiling and the expected values of
+ * mlh_trace_fill_public, loads and a compare where that call stores; the
+ * expected value of a SPARSE column's element by a binary search over the
+ * column's entries (at most 12 steps); the reduction of mlh_trace_check.  A
+ * pure function of the matrix and the spec.  Synchronises once. */
+mlh_status mlh_trace_check_public(mlh_ctx* ctx, const mlh_public_columns* spec,
+                                  const void* dev_matrix, uint32_t log_height, uint32_t width,
+                                  uint64_t* counts_out /* [F] or NULL */,
+                                  uint64_t* first_rows_out /* [F] or NULL */,
+                                  uint64_t* n_bad_rows, uint64_t* first_bad_row);
 
 /* ---- a lookup's multiplicities on the device -------------------------------- *
  * The multiplicity column m of a log-derivative lookup (v = -m / (gamma - t))

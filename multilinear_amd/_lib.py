@@ -122,6 +122,13 @@ ALL_GATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_uint64, ctypes.c_void_p)
 
 
+class TraceCheckReportC(ctypes.Structure):
+    """mlh_trace_check_report."""
+
+    _fields_ = [("n_bad_rows", ctypes.c_uint64), ("first_bad_row", ctypes.c_uint64),
+                ("first_bad_constraint", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class TransportC(ctypes.Structure):
     _fields_ = [
         ("world", ctypes.c_uint32),
@@ -310,6 +317,16 @@ SIGNATURES = {
     "mlh_trace_scan_launch_info": (_I, [_U32, _U32, _U32, ctypes.POINTER(_U32),
                                         ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     "mlh_trace_scan_shaped": (_I, [_P, _P, _U32, _U32, _U32, _P, _P, _P, _P, _P, _U32, _U32, _U32]),
+    "mlh_trace_check": (_I, [_P, _P, _P, _U32, _U32, ctypes.POINTER(_U32), _U32, _P,
+                             ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                             ctypes.POINTER(TraceCheckReportC)]),
+    "mlh_trace_check_launch_info": (_I, [_P, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "mlh_trace_check_shaped": (_I, [_P, _P, _P, _U32, _U32, ctypes.POINTER(_U32), _U32, _P,
+                                    ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                                    ctypes.POINTER(TraceCheckReportC), _U32, _U32]),
+    "mlh_trace_check_public": (_I, [_P, _P, _P, _U32, _U32, ctypes.POINTER(_U64),
+                                    ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                                    ctypes.POINTER(_U64)]),
     "mlh_trace_lookup_counts": (_I, [_P, _P, _U32, _U32, _U32, _U32, _U32, ctypes.POINTER(_U64),
                                      ctypes.POINTER(_U64)]),
     "mlh_trace_lookup_counts_launch_info": (_I, [_U32, _U32, ctypes.POINTER(_U32),

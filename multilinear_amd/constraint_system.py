@@ -35,7 +35,10 @@ by ``Trace.lookup_tuple_multiplicities`` (mlh_trace_lookup_tuple_counts);
 constraint.  The column a next-row constraint ``nxt(z) - z * t`` or ``nxt(z) -
 z - t`` holds (a grand product, a running sum) is written in phase 2 by
 ``PhasedProver.scan`` / ``Trace.scan`` (mlh_trace_scan), which also return the
-total across the cyclic wrap.
+total across the cyclic wrap.  Before ``prove``, ``PhasedProver.check`` /
+``Trace.check`` / ``Trace.check_public`` (mlh_trace_check, mlh_trace_check_public)
+say which constraint fails on how many rows and where first, and whether the
+public strip is the spec's.
 """
 import ctypes
 import struct
@@ -577,6 +580,43 @@ class Trace:
               ctx)
         return Trace(out, self._width + K)
 
+    def check(self, program, randoms=(), shift_columns=(), device=0, shape=None):
+        """Run every constraint of ``program`` (a Program of width + len(
+        shift_columns) columns, as compile_shifted gives it beside the list) on
+        every row, the shifted columns read from the next row, cyclically
+        (mlh_trace_check).  Returns a CheckResult; the trace is not modified.
+        shape = (threads, max_blocks): mlh_trace_check_shaped."""
+        cols, randoms = _check_arguments(self._width, program, randoms, shift_columns)
+        K, n = len(cols), program.n_constraints
+        counts, firsts = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)()
+        rep = _lib.TraceCheckReportC()
+        args = (program.h, ptr(self._matrix), self._height.bit_length() - 1, self._width,
+                (ctypes.c_uint32 * max(K, 1))(*cols), K, _elems(randoms), counts, firsts,
+                ctypes.byref(rep))
+        ctx = context(device)
+        if shape is None:
+            check(lib().mlh_trace_check(ctx, *args), ctx)
+        else:
+            check(lib().mlh_trace_check_shaped(ctx, *args, *shape), ctx)
+        return CheckResult(rep.n_bad_rows, rep.first_bad_row, rep.first_bad_constraint,
+                           list(counts), list(firsts))
+
+    def check_public(self, spec, device=0):
+        """The last len(spec) columns against what ``fill_public(spec)`` would
+        write (mlh_trace_check_public).  Returns a CheckResult per public
+        column; ``first_bad_constraint`` is the lowest column of the strip that
+        differs on the first bad row.  The trace is not modified."""
+        n = len(spec)
+        counts, firsts = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)()
+        bad, first = ctypes.c_uint64(), ctypes.c_uint64()
+        ctx = context(device)
+        check(lib().mlh_trace_check_public(ctx, spec.h, ptr(self._matrix),
+                                           self._height.bit_length() - 1, self._width, counts,
+                                           firsts, ctypes.byref(bad), ctypes.byref(first)), ctx)
+        firsts = list(firsts)
+        col = firsts.index(first.value) if bad.value else _NONE32
+        return CheckResult(bad.value, first.value, col, list(counts), firsts)
+
     def lookup_counts(self, value_columns, table_column, count_column, device=0):
         """A lookup's multiplicities, in place (mlh_trace_lookup_counts): column
         ``count_column`` of the lowest row holding each entry of ``table_column``
@@ -630,6 +670,57 @@ class Trace:
         if n:
             raise ValueError("%d looked-up tuple%s not in table columns %s, the first in row %d"
                              % (n, "" if n == 1 else "s", tuple(table_columns), first))
+
+
+_NONE64, _NONE32 = 2 ** 64 - 1, 2 ** 32 - 1
+
+
+class CheckResult:
+    """What Trace.check and Trace.check_public return.  bad_rows: the rows on
+    which anything fails; first_bad_row and first_bad_constraint: the lowest of
+    them and the lowest constraint (column of the strip) failing there, None
+    when clean; counts[c] / first_rows[c]: the failing rows of constraint c and
+    the lowest of them (None when none); ok: nothing fails."""
+
+    __slots__ = ("bad_rows", "first_bad_row", "first_bad_constraint", "counts", "first_rows")
+
+    def __init__(self, bad_rows, first_bad_row, first_bad_constraint, counts, first_rows):
+        self.bad_rows = bad_rows
+        self.first_bad_row = None if first_bad_row == _NONE64 else first_bad_row
+        self.first_bad_constraint = None if first_bad_constraint == _NONE32 else first_bad_constraint
+        self.counts = list(counts)
+        self.first_rows = [None if r == _NONE64 else r for r in first_rows]
+
+    @property
+    def ok(self):
+        return self.bad_rows == 0
+
+    def __repr__(self):
+        return ("CheckResult(bad_rows=%r, first_bad_row=%r, first_bad_constraint=%r, counts=%r, "
+                "first_rows=%r)" % (self.bad_rows, self.first_bad_row, self.first_bad_constraint,
+                                    self.counts, self.first_rows))
+
+
+def _check_arguments(width, program, randoms, shift_columns):
+    """The shift list and the randoms of Trace.check, checked (ValueError) as
+    mlh_trace_check checks them."""
+    cols, randoms = [int(c) for c in shift_columns], list(randoms)
+    for c in cols:
+        if not 0 <= c < width:
+            raise ValueError("source column %r outside the trace" % (c,))
+    if width + len(cols) != program.width:
+        raise ValueError("the program is %d columns wide, the trace %d and the shift list %d"
+                         % (program.width, width, len(cols)))
+    if len(randoms) != program.n_randoms:
+        raise ValueError("the program takes %d randoms" % program.n_randoms)
+    return cols, randoms
+
+
+def trace_check_launch_info(program, log_height):
+    """(threads per block, blocks) of mlh_trace_check."""
+    t, b = ctypes.c_uint32(), ctypes.c_uint32()
+    check(lib().mlh_trace_check_launch_info(program.h, log_height, ctypes.byref(t), ctypes.byref(b)))
+    return t.value, b.value
 
 
 LOOKUP_MAX_ARITY, LOOKUP_MAX_TUPLES, LOOKUP_NO_SELECTOR = 8, 16, 0xFFFFFFFF
@@ -1126,6 +1217,19 @@ class PhasedProver:
             if self._committed <= d < lay.columns:
                 raise ValueError("scan writes the public column %d" % d)
         return self._trace.scan(scans, self._device)
+
+    def check(self):
+        """The witness check of the trace as it stands, before ``prove``: the
+        prover's own program with ``self.shift_columns`` and ``self.randoms``
+        (Trace.check), and with public columns in the layout the strip against
+        its spec (Trace.check_public).  Returns (constraints, public), each a
+        CheckResult, public None without public columns.  No transcript is
+        touched."""
+        res = self._trace.check(self.program, self.randoms, self.shift_columns, self._device)
+        pub = None
+        if self._public is not None:
+            pub = self._trace.check_public(self._public, self._device)
+        return res, pub
 
     def prove(self, transcript, total_sum, column_sum=None):
         """mlh_system_prove_phased on a clone of the trace's matrix.

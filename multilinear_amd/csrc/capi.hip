@@ -46,6 +46,7 @@
 #include "sumcheck.hpp"
 #include "system_head.hpp"
 #include "tables.hpp"
+#include "trace_check.hpp"
 #include "trace_commit.hpp"
 #include "trace_fill.hpp"
 #include "trace_lookup.hpp"
@@ -2024,6 +2025,153 @@ mlh_status mlh_system_prove_shifted(mlh_ctx* ctx, const mlh_cs_program* prog,
                                     mlh_shifted_proof* proof) {
   return mlh_system_prove_public(ctx, prog, com1, com2, sum_column_mask, shift_columns, n_shifts,
                                  nullptr, dev_matrix, sum, column_sum, tr, proof);
+}
+
+}  // extern "C"
+
+// ---- the witness check (trace_check.hip, trace_public.hip; mlhip.h gives the semantics) ----
+
+// Zeroes the counts and the row count and sets the first rows to all ones,
+// behind the pool's poison fill on the stream (tk_counter_words' layout).
+static mlh_status check_counters_init(mlh_ctx* ctx, PoolBuf& buf, uint32_t n) {
+  MLH_TRY(buf.alloc(8 * tk_counter_words(n)));
+  uint8_t* p = buf.as<uint8_t>();
+  HIP_TRY(ctx, hipMemsetAsync(p, 0, 8ull * (n + 1), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(p + 8ull * (n + 1), 0xFF, 8ull * n, ctx->stream));
+  return MLH_OK;
+}
+
+// The one wait of a check: the counters to the host; counts / first rows to
+// the caller's arrays where given.  -> the rows with any failure and the first
+// rows (n of them, in `firsts`).
+static mlh_status check_counters_read(mlh_ctx* ctx, const PoolBuf& buf, uint32_t n,
+                                      uint64_t* counts_out, uint64_t* first_rows_out,
+                                      uint64_t* n_bad, std::vector<uint64_t>& firsts) {
+  const size_t bytes = 8 * tk_counter_words(n);
+  static_assert(8 * (2 * kCsMaxConstraints + 1) <= kPinnedBytes, "the counters fit the staging buffer");
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, buf.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<uint64_t> w(tk_counter_words(n));
+  memcpy(w.data(), ctx->pinned, bytes);
+  firsts.assign(w.begin() + n + 1, w.end());
+  if (counts_out) memcpy(counts_out, w.data(), 8ull * n);
+  if (first_rows_out) memcpy(first_rows_out, firsts.data(), 8ull * n);
+  *n_bad = w[n];
+  return MLH_OK;
+}
+
+static mlh_status trace_check_run(mlh_ctx* ctx, const mlh_cs_program* prog, const void* dev_matrix,
+                                  uint32_t log_height, uint32_t width, const uint32_t* shift_columns,
+                                  uint32_t n_shifts, const uint8_t* host_randoms,
+                                  uint64_t* counts_out, uint64_t* first_rows_out,
+                                  mlh_trace_check_report* report, bool shaped, uint32_t threads,
+                                  uint32_t max_blocks) {
+  if (!ctx || !prog || !dev_matrix || !report || (n_shifts && !shift_columns))
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check: null argument");
+  const CsProgram& p = prog->p;
+  if (width < 1 || width > kCsMaxWidth || n_shifts > kCsMaxWidth || width + n_shifts != p.width ||
+      log_height > kCsMaxLogHeight)
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check: width 1..32, width + n_shifts the program's "
+                                      "width (at most 32), log_height 0..32");
+  for (uint32_t k = 0; k < n_shifts; ++k)
+    if (shift_columns[k] >= width)
+      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check: source column outside the trace");
+  if (p.n_randoms && !host_randoms) return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check: randoms missing");
+  const uint64_t H = 1ull << log_height;
+  uint32_t blocks;
+  if (shaped) {
+    if (!tk_shape_ok(tk_slots(p), threads, max_blocks))
+      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check_shaped: threads 64, 128 or 256 whose slots "
+                                        "fit 152 KiB of LDS, max_blocks 1..1024");
+    blocks = tk_blocks_shaped(H, threads, max_blocks);
+  } else {
+    threads = cs_threads(tk_slots(p));
+    blocks = tk_blocks(H, threads);
+  }
+  const uint32_t NC = p.n_constraints;
+  const std::vector<uint8_t> no_mask(16ull * NC, 0);  // (the mask plays no part: its pool entries are zero)
+  CsCall cc(ctx);
+  MLH_TRY(cc.init(ctx, prog, host_randoms, no_mask.data()));  // (checks the randoms before it enqueues)
+  PoolBuf counters(ctx);
+  MLH_TRY(check_counters_init(ctx, counters, NC));
+  ProfScope ps(ctx, "trace_check");
+  HIP_TRY(ctx, launch_trace_check(cc.dev, reinterpret_cast<const fe*>(dev_matrix), log_height, width,
+                                  shift_columns, n_shifts, counters.as<uint64_t>(), threads, blocks,
+                                  ctx->stream));
+  ps.end();
+  std::vector<uint64_t> firsts;
+  uint64_t n_bad = 0;
+  MLH_TRY(check_counters_read(ctx, counters, NC, counts_out, first_rows_out, &n_bad, firsts));
+  report->n_bad_rows = n_bad;
+  report->first_bad_row = UINT64_MAX;
+  report->first_bad_constraint = UINT32_MAX;
+  report->reserved = 0;
+  for (uint32_t c = 0; c < NC; ++c)
+    if (firsts[c] < report->first_bad_row) {
+      report->first_bad_row = firsts[c];
+      report->first_bad_constraint = c;
+    }
+  return MLH_OK;
+}
+
+extern "C" {
+
+mlh_status mlh_trace_check(mlh_ctx* ctx, const mlh_cs_program* prog, const void* dev_matrix,
+                           uint32_t log_height, uint32_t width, const uint32_t* shift_columns,
+                           uint32_t n_shifts, const uint8_t* host_randoms, uint64_t* counts_out,
+                           uint64_t* first_rows_out, mlh_trace_check_report* report) {
+  return trace_check_run(ctx, prog, dev_matrix, log_height, width, shift_columns, n_shifts,
+                         host_randoms, counts_out, first_rows_out, report, false, 0, 0);
+}
+
+mlh_status mlh_trace_check_shaped(mlh_ctx* ctx, const mlh_cs_program* prog, const void* dev_matrix,
+                                  uint32_t log_height, uint32_t width,
+                                  const uint32_t* shift_columns, uint32_t n_shifts,
+                                  const uint8_t* host_randoms, uint64_t* counts_out,
+                                  uint64_t* first_rows_out, mlh_trace_check_report* report,
+                                  uint32_t threads, uint32_t max_blocks) {
+  return trace_check_run(ctx, prog, dev_matrix, log_height, width, shift_columns, n_shifts,
+                         host_randoms, counts_out, first_rows_out, report, true, threads, max_blocks);
+}
+
+mlh_status mlh_trace_check_launch_info(const mlh_cs_program* prog, uint32_t log_height,
+                                       uint32_t* threads, uint32_t* blocks) {
+  if (!prog || !threads || !blocks || log_height > kCsMaxLogHeight) return MLH_ERR_INVALID;
+  *threads = cs_threads(tk_slots(prog->p));
+  *blocks = tk_blocks(1ull << log_height, *threads);
+  return MLH_OK;
+}
+
+mlh_status mlh_trace_check_public(mlh_ctx* ctx, const mlh_public_columns* spec,
+                                  const void* dev_matrix, uint32_t log_height, uint32_t width,
+                                  uint64_t* counts_out, uint64_t* first_rows_out,
+                                  uint64_t* n_bad_rows, uint64_t* first_bad_row) {
+  if (!ctx || !spec || !dev_matrix || !n_bad_rows || !first_bad_row)
+    return fail(ctx, MLH_ERR_INVALID, "null argument");
+  const PublicColumns& s = spec->p;
+  if (width < 1 || width > kTpMaxWidth || s.count() > width || log_height > kCsMaxLogHeight)
+    return fail(ctx, MLH_ERR_INVALID, "width 1..32, at most width public columns, log_height 0..32");
+  if (!s.fits(log_height))
+    return fail(ctx, MLH_ERR_INVALID, "a period or a sparse row of the spec is beyond the height");
+  const uint32_t F = s.count();
+  PoolBuf img(ctx), counters(ctx);
+  MLH_TRY(img.alloc(s.image.size()));
+  HIP_TRY(ctx, hipMemcpyAsync(img.p, s.image.data(), s.image.size(), hipMemcpyHostToDevice,
+                              ctx->stream));
+  MLH_TRY(check_counters_init(ctx, counters, F));
+  ProfScope ps(ctx, "trace_check_public");
+  HIP_TRY(ctx, launch_trace_check_public(reinterpret_cast<const fe*>(dev_matrix), img.p, F,
+                                         s.sparse_off, log_height, width, counters.as<uint64_t>(),
+                                         ctx->stream));
+  ps.end();
+  std::vector<uint64_t> firsts;
+  uint64_t n_bad = 0;
+  MLH_TRY(check_counters_read(ctx, counters, F, counts_out, first_rows_out, &n_bad, firsts));
+  *n_bad_rows = n_bad;
+  *first_bad_row = UINT64_MAX;
+  for (uint64_t f : firsts)
+    if (f < *first_bad_row) *first_bad_row = f;
+  return MLH_OK;
 }
 
 }  // extern "C"

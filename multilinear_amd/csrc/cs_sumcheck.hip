@@ -34,6 +34,7 @@
 // lin[gridDim.x + block], and cs_round_lin_kernel adds beta (A + (t - 1) B)
 // to evals[t].  SUMS = false is the code without any of it.
 #include "bfly_asm.hpp"
+#include "cs_interp.hpp"
 #include "cs_program.hpp"
 #include "cs_sumcheck.hpp"
 #include "field.hpp"
@@ -44,26 +45,8 @@ namespace mlh {
 
 constexpr uint32_t kCsMaxD = kCsMaxDegree + 1;
 
-// (row, column) of the elements tid, tid + B, tid + 2B, ... of a chunk
-struct CsWalk {
-  uint32_t row, col, srow, scol, W;
-  __device__ __forceinline__ CsWalk(uint32_t tid, uint32_t B, uint32_t W_)
-      : row(tid / W_), col(tid % W_), srow(B / W_), scol(B % W_), W(W_) {}
-  __device__ __forceinline__ void next() {
-    row += srow;
-    col += scol;
-    if (col >= W) {
-      col -= W;
-      ++row;
-    }
-  }
-};
-
-__device__ __forceinline__ fe cs_fetch(uint32_t o, const fe* __restrict__ uni, const fe* lane_lds,
-                                       uint32_t B) {
-  if (o & kCsUniform) return fe_vgpr(uni[o & 0x7FFFu]);
-  return lane_lds[o * B];
-}
+// (CsWalk, cs_fetch and the interpreter's step cs_step: cs_interp.hpp, shared with
+// trace_check.hip)
 
 // The D sums of one chunk: lane_lds = this lane's column of the LDS slots
 // (filled with the values at X = 1 and the steps), dc / dd = delta at X = 1
@@ -72,24 +55,7 @@ __device__ __forceinline__ void cs_accumulate(const CsDev& P, fe* lane_lds, uint
                                               fe dc, const fe& dd) {
   const uint32_t W = P.width, step0 = W + P.n_temps, acc0 = step0 + W;
   for (uint32_t t = 0; t < P.D; ++t) {
-    for (uint32_t pc = 0; pc < P.n_instr; ++pc) {
-      const uint32_t w0 = P.code[2 * pc], w1 = P.code[2 * pc + 1];
-      const uint32_t op = w0 & 0xFFu;
-      const fe a = cs_fetch(w1 & 0xFFFFu, P.uni, lane_lds, B);
-      fe r;
-      if (op == kCsNeg) {
-        r = fe_neg(a);
-      } else {
-        const fe b = cs_fetch(w1 >> 16, P.uni, lane_lds, B);
-        if (op == kCsMul)
-          r = fe_mul_s(a, b);
-        else if (op == kCsAdd)
-          r = fe_add(a, b);
-        else
-          r = fe_sub(a, b);
-      }
-      lane_lds[(w0 >> 8) * B] = r;
-    }
+    for (uint32_t pc = 0; pc < P.n_instr; ++pc) cs_step(P, lane_lds, B, pc);
     fe c = fe_zero();  // sum_c mask[c] * out_c (evaluation.rs:21-29)
     for (uint32_t k = 0; k < P.n_constraints; ++k) {
       const uint32_t o = P.outs[k];

@@ -22,9 +22,11 @@ enum : uint32_t { kPcConst = 0, kPcFirst = 1, kPcLast = 2, kPcRow = 3, kPcPeriod
 constexpr uint32_t kPcMaxColumns = 16, kPcMaxLogPeriod = 16, kPcMaxSparse = 4096;
 constexpr uint32_t kPcMaxLogHeight = 32;
 // The device image, in 16-byte words: two per column slot -- {kind, period
-// mask, table offset, 0} and the constant (zero unless CONST) -- for all
-// kPcMaxColumns slots, then the periodic tables, then two per sparse entry --
-// {row low, row high, column of the strip, 0} and the value.  A column that
+// mask, table offset, sparse range} and the constant (zero unless CONST) --
+// for all kPcMaxColumns slots, then the periodic tables, then two per sparse
+// entry -- {row low, row high, column of the strip, 0} and the value, column
+// after column and by ascending row within one.  The sparse range of a SPARSE
+// column is the index of its first entry | its count << 16 (zero otherwise).  A column that
 // is not periodic has mask 0 and its own constant word as its table, so that
 // word (off + (row & mask)) is the element's base value for every kind.
 constexpr uint32_t kPcDescWords = 2 * kPcMaxColumns;
@@ -86,7 +88,9 @@ static inline void pc_build_image(PublicColumns& s) {
       pc_wr32(d + 8, table);
       for (const u128 v : c.values) h_store(img + 16ull * table++, v);
     }
-    if (c.kind == kPcSparse)
+    if (c.kind == kPcSparse) {
+      // (the check's search: this column's first entry | count << 16; at most 16 * 4096 entries)
+      pc_wr32(d + 12, ((entry - s.sparse_off) / 2) | ((uint32_t)c.rows.size() << 16));
       for (size_t m = 0; m < c.rows.size(); ++m, entry += 2) {
         uint8_t* e = img + 16ull * entry;
         pc_wr32(e, (uint32_t)c.rows[m]);
@@ -94,6 +98,7 @@ static inline void pc_build_image(PublicColumns& s) {
         pc_wr32(e + 8, j);
         h_store(e + 16, c.values[m]);
       }
+    }
   }
 }
 

@@ -37,4 +37,14 @@ hipError_t launch_trace_fill_public(fe* matrix, const void* image, uint32_t F, u
                                     uint32_t n_sparse, uint32_t log_height, uint32_t width,
                                     hipStream_t st);
 
+// The strip of the matrix against the spec's image, nothing written: counters
+// (2 F + 1 64-bit words: [0, F) the differing rows per column, [F] the rows
+// with any difference, [F + 1, 2 F + 1) the lowest differing row per column,
+// all ones when none; the caller zeroes the first F + 1 and sets the rest to
+// all ones on the stream before the launch).  The limits of
+// launch_trace_fill_public.
+hipError_t launch_trace_check_public(const fe* matrix, const void* image, uint32_t F,
+                                     uint32_t sparse_off, uint32_t log_height, uint32_t width,
+                                     uint64_t* counters, hipStream_t st);
+
 }  // namespace mlh
