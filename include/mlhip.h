@@ -1180,6 +1180,83 @@ mlh_status mlh_trace_scan_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_he
                                  const uint8_t* host_inits, uint8_t* totals_out, uint32_t threads,
                                  uint32_t rows_per_thread, uint32_t max_blocks);
 
+/* ---- sorted copies of columns on the device ---------------------------------- *
+ * The log of a memory-consistency argument in address-then-timestamp order, the
+ * sorted column of a range check by differences, the second side of a multiset
+ * argument "the same rows, ordered": a sorted copy of columns, written in place
+ * with no host copy of a column.
+ * Let H = 2^log_height and key(i) the tuple of the 16-byte elements
+ * matrix[i][key_columns[0 .. n_keys - 1]] as the matrix stood when the call
+ * began, each read as an unsigned 128-bit little-endian integer (canonical
+ * input is the caller's contract, as in the lookup calls; the order is that of
+ * the 16 bytes as an integer).  pi is the one permutation of 0..H-1 with
+ * key(pi(0)) <= key(pi(1)) <= ... lexicographically, key_columns[0] the most
+ * significant, and pi(r) < pi(r + 1) wherever the keys are equal: the stable
+ * ascending sort.  There is no descending flag.  After the call, for r < H,
+ *   matrix[r][dst_columns[s]] = old matrix[pi(r)][src_columns[s]], s < n_copies;
+ *   matrix[r][perm_column]    = pi(r) as a canonical element, when perm_column
+ *                               is not MLH_SORT_NO_COLUMN: the index column that
+ *                               a permutation argument over (value, row) pairs
+ *                               needs;
+ *   *passes_out               = the number of digit passes that ran (below);
+ * and no other byte of the matrix is written.  A key column may also be a
+ * source (the usual case) and a source may repeat.  Destination columns and
+ * perm_column are pairwise distinct and disjoint from every key and source
+ * column, so the gather is in place with no staging copy.  The result is a pure
+ * function of the matrix and the column lists: it does not depend on the launch
+ * shape.
+ * width 1..32, log_height 0..28 (row indices are 32-bit, as in
+ * mlh_trace_lookup_counts), n_keys 1..4, n_copies 0..16, and at least one
+ * output: n_copies > 0 or a perm_column.  A column at or above width, an
+ * overlap that the rules above forbid, a limit exceeded and a NULL ctx,
+ * dev_matrix, key_columns, or src_columns / dst_columns with n_copies > 0, are
+ * MLH_ERR_INVALID before anything is enqueued: the matrix is untouched.
+ * passes_out may be NULL.
+ * An LSD radix sort with 8-bit digits over (32-bit key limb, row index) pairs,
+ * every step a launch on the context stream, none of which waits for another
+ * workgroup.  A digit census (one pass over the key columns: LDS tables per
+ * block, one 32-bit atomic add per non-empty bin) counts all 16 n_keys digits
+ * at once; the call then synchronises once to learn which digits all H rows
+ * agree in, and skips those (keys below 2^32 leave at most 4 of a key's 16
+ * passes; H = 1 or all keys equal leave none, and the gather alone runs with
+ * pi the identity).  A limb is gathered from the matrix once and serves its up
+ * to four digit passes; a pass is a per-block histogram, a one-block exclusive
+ * scan of the blocks x 256 table in digit-major order behind the census's digit
+ * starts, and a stable scatter (a block walks its consecutive tiles in order,
+ * ranks by wave ballots); one last launch gathers the copies with 16-byte loads
+ * and stores.  Scratch, pooled: 16 bytes per row (two arrays of pairs), 16 KiB
+ * per key (the census), 2 KiB per block and 256 bytes. */
+#define MLH_SORT_MAX_KEYS   4
+#define MLH_SORT_MAX_COPIES 16
+#define MLH_SORT_NO_COLUMN  0xFFFFFFFFu
+mlh_status mlh_trace_sort(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height, uint32_t width,
+                          uint32_t n_keys, const uint32_t* key_columns /* most significant first */,
+                          uint32_t n_copies, const uint32_t* src_columns,
+                          const uint32_t* dst_columns,
+                          uint32_t perm_column /* or MLH_SORT_NO_COLUMN */,
+                          uint32_t* passes_out /* or NULL */);
+/* Its launch shape: threads per block (256), rows per thread (8) and blocks
+ * (min(ceil(2^log_height / (threads * rows_per_thread)), 1024)); a block takes
+ * ceil(tiles / blocks) consecutive tiles of threads * rows_per_thread rows, the
+ * last blocks fewer or none.  In a tile a wave owns 64 * rows_per_thread
+ * consecutive rows and lane j of it the rows j, j + 64, ...  width 1..32,
+ * log_height 0..28, n_keys 1..4. */
+mlh_status mlh_trace_sort_launch_info(uint32_t log_height, uint32_t width, uint32_t n_keys,
+                                      uint32_t* threads, uint32_t* rows_per_thread,
+                                      uint32_t* blocks);
+/* The same kernels and the same bytes under another shape, for tests of the
+ * seams at small heights and for measurements: threads 64, 128 or 256,
+ * rows_per_thread a power of two up to 16, max_blocks 1..1024 (the grid is
+ * min(tiles, max_blocks) blocks).  flags bit 0: run every digit pass, skip
+ * none (*passes_out = 16 n_keys; the call then does not wait for the device);
+ * any other bit, and any other shape, is MLH_ERR_INVALID. */
+mlh_status mlh_trace_sort_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                 uint32_t width, uint32_t n_keys, const uint32_t* key_columns,
+                                 uint32_t n_copies, const uint32_t* src_columns,
+                                 const uint32_t* dst_columns, uint32_t perm_column,
+                                 uint32_t* passes_out, uint32_t threads, uint32_t rows_per_thread,
+                                 uint32_t max_blocks, uint32_t flags);
+
 /* ---- the witness check on the device ---------------------------------------- *
  * The provers do not detect a trace that breaks a constraint or a public strip
  * that differs from its spec: they return MLH_OK and the verifier rejects.

@@ -317,6 +317,13 @@ SIGNATURES = {
     "mlh_trace_scan_launch_info": (_I, [_U32, _U32, _U32, ctypes.POINTER(_U32),
                                         ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     "mlh_trace_scan_shaped": (_I, [_P, _P, _U32, _U32, _U32, _P, _P, _P, _P, _P, _U32, _U32, _U32]),
+    "mlh_trace_sort": (_I, [_P, _P, _U32, _U32, _U32, ctypes.POINTER(_U32), _U32,
+                            ctypes.POINTER(_U32), ctypes.POINTER(_U32), _U32, ctypes.POINTER(_U32)]),
+    "mlh_trace_sort_launch_info": (_I, [_U32, _U32, _U32, ctypes.POINTER(_U32),
+                                        ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "mlh_trace_sort_shaped": (_I, [_P, _P, _U32, _U32, _U32, ctypes.POINTER(_U32), _U32,
+                                   ctypes.POINTER(_U32), ctypes.POINTER(_U32), _U32,
+                                   ctypes.POINTER(_U32), _U32, _U32, _U32, _U32]),
     "mlh_trace_check": (_I, [_P, _P, _P, _U32, _U32, ctypes.POINTER(_U32), _U32, _P,
                              ctypes.POINTER(_U64), ctypes.POINTER(_U64),
                              ctypes.POINTER(TraceCheckReportC)]),

@@ -35,9 +35,11 @@ by ``Trace.lookup_tuple_multiplicities`` (mlh_trace_lookup_tuple_counts);
 constraint.  The column a next-row constraint ``nxt(z) - z * t`` or ``nxt(z) -
 z - t`` holds (a grand product, a running sum) is written in phase 2 by
 ``PhasedProver.scan`` / ``Trace.scan`` (mlh_trace_scan), which also return the
-total across the cyclic wrap.  Before ``prove``, ``PhasedProver.check`` /
-``Trace.check`` / ``Trace.check_public`` (mlh_trace_check, mlh_trace_check_public)
-say which constraint fails on how many rows and where first, and whether the
+total across the cyclic wrap.  A sorted copy of columns (a memory log in
+address-then-timestamp order, the ordered side of a multiset argument) is
+written by ``PhasedProver.sort`` / ``Trace.sort`` (mlh_trace_sort).  Before
+``prove``, ``PhasedProver.check`` / ``Trace.check`` / ``Trace.check_public``
+(mlh_trace_check, mlh_trace_check_public) say which constraint fails on how many rows and where first, and whether the
 public strip is the spec's.
 """
 import ctypes
@@ -566,6 +568,28 @@ class Trace:
                                    _elems(inits), out), ctx)
         return _split(out, n) if totals else None
 
+    def sort(self, keys, copies, perm_column=None, device=0, shape=None):
+        """Sorted copies of columns, in place (mlh_trace_sort).  ``keys``: 1 to
+        4 key columns, the most significant first, compared as unsigned 128-bit
+        integers; ``copies``: up to 16 (src, dst) pairs: column dst becomes
+        column src in stable ascending key order; ``perm_column`` (or None)
+        receives the source row of every sorted row.  ``shape``: None for the
+        default launch, or (threads, rows_per_thread, max_blocks[, flags]) for
+        mlh_trace_sort_shaped.  Returns the number of digit passes that ran."""
+        key, src, dst, perm = _sort_arrays(keys, copies, perm_column, self._width)
+        u32s = lambda v: (ctypes.c_uint32 * max(len(v), 1))(*v)
+        passes = ctypes.c_uint32()
+        ctx = context(device)
+        args = (ctx, ptr(self._matrix), self._height.bit_length() - 1, self._width, len(key),
+                u32s(key), len(src), u32s(src), u32s(dst), perm, ctypes.byref(passes))
+        if shape is None:
+            check(lib().mlh_trace_sort(*args), ctx)
+        else:
+            threads, rows, max_blocks = shape[:3]
+            flags = shape[3] if len(shape) > 3 else 0
+            check(lib().mlh_trace_sort_shaped(*args, threads, rows, max_blocks, flags), ctx)
+        return passes.value
+
     def extend_next(self, shift_columns, device=0):
         """The extension of a shifted system (mlh_trace_extend_next): a new
         Trace of width + len(shift_columns) columns whose column width + k is
@@ -852,6 +876,42 @@ def trace_scan_launch_info(log_height, width, n_scans):
     """(threads per block, consecutive rows per thread, blocks) of mlh_trace_scan."""
     t, k, b = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
     check(lib().mlh_trace_scan_launch_info(log_height, width, n_scans, ctypes.byref(t),
+                                           ctypes.byref(k), ctypes.byref(b)))
+    return t.value, k.value, b.value
+
+
+SORT_MAX_KEYS, SORT_MAX_COPIES, SORT_NO_COLUMN = 4, 16, 0xFFFFFFFF
+
+
+def _sort_arrays(keys, copies, perm_column, width):
+    """(keys, sources, destinations, perm column or SORT_NO_COLUMN) of a sort,
+    checked as mlh_trace_sort checks them."""
+    keys = [int(k) for k in keys]
+    copies = [(int(s), int(d)) for s, d in copies]
+    if not 1 <= len(keys) <= SORT_MAX_KEYS:
+        raise ValueError("1 to %d key columns, not %d" % (SORT_MAX_KEYS, len(keys)))
+    if len(copies) > SORT_MAX_COPIES:
+        raise ValueError("at most %d copies in one call, not %d" % (SORT_MAX_COPIES, len(copies)))
+    if not copies and perm_column is None:
+        raise ValueError("a sort needs an output: a copy or a perm_column")
+    src, dst = [s for s, _ in copies], [d for _, d in copies]
+    written = dst + ([int(perm_column)] if perm_column is not None else [])
+    for name, cols in (("key", keys), ("source", src), ("destination", written)):
+        for j in cols:
+            if not 0 <= j < width:
+                raise ValueError("%s column %r outside the trace" % (name, j))
+    if len(set(written)) != len(written):
+        raise ValueError("destination columns and perm_column must be pairwise distinct")
+    both = set(written) & (set(keys) | set(src))
+    if both:
+        raise ValueError("column %d is written and is a key or a source" % min(both))
+    return keys, src, dst, SORT_NO_COLUMN if perm_column is None else int(perm_column)
+
+
+def trace_sort_launch_info(log_height, width, n_keys):
+    """(threads per block, rows per thread, blocks) of mlh_trace_sort."""
+    t, k, b = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    check(lib().mlh_trace_sort_launch_info(log_height, width, n_keys, ctypes.byref(t),
                                            ctypes.byref(k), ctypes.byref(b)))
     return t.value, k.value, b.value
 
@@ -1217,6 +1277,21 @@ class PhasedProver:
             if self._committed <= d < lay.columns:
                 raise ValueError("scan writes the public column %d" % d)
         return self._trace.scan(scans, self._device)
+
+    def sort(self, keys, copies, perm_column=None):
+        """``Trace.sort`` on the prover's trace: sorted copies into columns at
+        and above pre_random_columns and below the public strip; returns the
+        number of digit passes.  A destination (or perm_column) that
+        commitment 1 already holds, or a public column: ValueError."""
+        lay = self._layout
+        copies = list(copies)
+        for d in [d for _, d in copies] + ([perm_column] if perm_column is not None else []):
+            if 0 <= d < lay.pre_random_columns:
+                raise ValueError("sort writes column %d below pre_random_columns (%d), which "
+                                 "commitment 1 already holds" % (d, lay.pre_random_columns))
+            if self._committed <= d < lay.columns:
+                raise ValueError("sort writes the public column %d" % d)
+        return self._trace.sort(keys, copies, perm_column, self._device)
 
     def check(self):
         """The witness check of the trace as it stands, before ``prove``: the

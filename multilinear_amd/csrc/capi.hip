@@ -52,6 +52,7 @@
 #include "trace_lookup.hpp"
 #include "trace_public.hpp"
 #include "trace_scan.hpp"
+#include "trace_sort.hpp"
 #include "trace_shift.hpp"
 #include "transcript_dev.hpp"
 
@@ -1361,6 +1362,106 @@ mlh_status mlh_trace_scan_launch_info(uint32_t log_height, uint32_t width, uint3
   *threads = kScanThreads;
   *rows_per_thread = kScanRowsPerThread;
   *blocks = scan_blocks(scan_tiles(1ull << log_height, kScanThreads, kScanRowsPerThread),
+                        kScanMaxBlocks);
+  return MLH_OK;
+}
+
+// ---- sorted copies of columns (trace_sort.hip) ----
+
+static_assert(MLH_SORT_MAX_KEYS == kSortMaxKeys && MLH_SORT_MAX_COPIES == kSortMaxCopies &&
+                  MLH_SORT_NO_COLUMN == kSortNoColumn,
+              "mlhip.h and trace_sort.hpp agree");
+
+static bool sort_dims_ok(uint32_t log_height, uint32_t width, uint32_t n_keys) {
+  return log_height <= kSortMaxLogHeight && width >= 1 && width <= kCsMaxWidth && n_keys >= 1 &&
+         n_keys <= kSortMaxKeys;
+}
+
+mlh_status mlh_trace_sort_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
+                                 uint32_t width, uint32_t n_keys, const uint32_t* key_columns,
+                                 uint32_t n_copies, const uint32_t* src_columns,
+                                 const uint32_t* dst_columns, uint32_t perm_column,
+                                 uint32_t* passes_out, uint32_t threads, uint32_t rows_per_thread,
+                                 uint32_t max_blocks, uint32_t flags) {
+  if (!ctx || !dev_matrix || !key_columns || !sort_dims_ok(log_height, width, n_keys) ||
+      n_copies > kSortMaxCopies || (n_copies && (!src_columns || !dst_columns)) ||
+      (!n_copies && perm_column == kSortNoColumn) ||
+      !scan_shape_ok(threads, rows_per_thread, max_blocks) || (flags & ~kSortRunAll))
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: bad argument");
+  SortArgs a{};
+  uint32_t read = 0, written = 0;  // column masks
+  for (uint32_t k = 0; k < n_keys; ++k) {
+    if (key_columns[k] >= width)
+      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: key column out of range");
+    read |= 1u << key_columns[k];
+    a.key[k] = (uint8_t)key_columns[k];
+  }
+  for (uint32_t s = 0; s < n_copies; ++s) {
+    if (src_columns[s] >= width || dst_columns[s] >= width || ((written >> dst_columns[s]) & 1u))
+      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: column out of range or destination "
+                                        "written twice");
+    read |= 1u << src_columns[s];
+    written |= 1u << dst_columns[s];
+    a.src[s] = (uint8_t)src_columns[s];
+    a.dst[s] = (uint8_t)dst_columns[s];
+  }
+  if (perm_column != kSortNoColumn) {
+    if (perm_column >= width || ((written >> perm_column) & 1u))
+      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: perm_column out of range or a destination");
+    written |= 1u << perm_column;
+  }
+  if (read & written)
+    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: a destination is a key or a source");
+  a.m = reinterpret_cast<fe*>(dev_matrix);
+  a.height = 1ull << log_height;
+  a.width = width;
+  a.n_keys = n_keys;
+  a.n_copies = n_copies;
+  a.perm_column = perm_column;
+  a.threads = threads;
+  a.rows_per_thread = rows_per_thread;
+  a.tiles = scan_tiles(a.height, threads, rows_per_thread);
+  a.blocks = scan_blocks(a.tiles, max_blocks);
+  a.tiles_per_block = (a.tiles + a.blocks - 1) / a.blocks;
+  PoolBuf scratch(ctx);  // the pairs, the census and one pass's tables
+  MLH_TRY(scratch.alloc(sort_scratch_bytes(a.height, n_keys, a.blocks)));
+  sort_carve(a, scratch.p);
+  const uint32_t digits = kSortDigitsPerKey * n_keys;
+  ProfScope ps(ctx, "trace_sort");
+  HIP_TRY(ctx, launch_sort_census(a, ctx->stream));
+  uint64_t run = digits == 64 ? ~0ull : (1ull << digits) - 1;
+  if (!(flags & kSortRunAll)) {  // drop the digits in which all rows agree
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, a.same, 4ull * digits, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t same[kSortDigitsPerKey * kSortMaxKeys];
+    memcpy(same, ctx->pinned, 4ull * digits);
+    for (uint32_t g = 0; g < digits; ++g)
+      if (same[g]) run &= ~(1ull << g);
+  }
+  HIP_TRY(ctx, launch_sort_passes(a, run, ctx->stream));
+  ps.end();
+  if (passes_out) *passes_out = (uint32_t)__builtin_popcountll(run);
+  return MLH_OK;  // (the scratch's next user is behind these launches)
+}
+
+mlh_status mlh_trace_sort(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height, uint32_t width,
+                          uint32_t n_keys, const uint32_t* key_columns, uint32_t n_copies,
+                          const uint32_t* src_columns, const uint32_t* dst_columns,
+                          uint32_t perm_column, uint32_t* passes_out) {
+  return mlh_trace_sort_shaped(ctx, dev_matrix, log_height, width, n_keys, key_columns, n_copies,
+                               src_columns, dst_columns, perm_column, passes_out, kSortThreads,
+                               kSortRowsPerThread, kScanMaxBlocks, 0);
+}
+
+mlh_status mlh_trace_sort_launch_info(uint32_t log_height, uint32_t width, uint32_t n_keys,
+                                      uint32_t* threads, uint32_t* rows_per_thread,
+                                      uint32_t* blocks) {
+  if (!threads || !rows_per_thread || !blocks || !sort_dims_ok(log_height, width, n_keys))
+    return MLH_ERR_INVALID;
+  *threads = kSortThreads;
+  *rows_per_thread = kSortRowsPerThread;
+  *blocks = scan_blocks(scan_tiles(1ull << log_height, kSortThreads, kSortRowsPerThread),
                         kScanMaxBlocks);
   return MLH_OK;
 }
