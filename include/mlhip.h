@@ -13,6 +13,10 @@
  *     (merkle_tree/mod.rs:7-11);
  *   - "dev" pointers are device (HBM) pointers on the context's device, e.g.
  *     from mlh_malloc or any HIP allocator; "host" pointers are host memory.
+ *   - Device pointers to field elements and digests must be 16-byte aligned;
+ *     nothing more is assumed, so a caller may pass interior pointers of an
+ *     arena of its own.  A call reads and writes only the byte ranges its
+ *     comment gives.
  *   - All work is enqueued on the context's HIP stream; functions that return
  *     host results (roots, sums, proofs) synchronise that stream.
  *
