@@ -1,13 +1,13 @@
 // C ABI (include/mlhip.h) and the C++ host layer above the gfx950 kernels:
 // host orchestration only, no kernel lives here.
-//
 // Here: the context, the pool and the twiddle-table cache, the NTT /
 // Reed-Solomon / Merkle / field entries, the stepwise sumcheck entries, the
-// trace commitment, the phase-2 fill, column sum and column scans, the constraint-system
-// sumcheck and the system proofs.
-// The FRI prover is fri_prover.hip; the sumcheck, PCS and batched-PCS provers
-// above it, pcs_prover.hip; the multi-GPU schedules, sharded.hip, and their
-// rank-local steps, shard_steps.hip; verifiers and host transcript, verify.cpp.
+// trace commitment, the constraint-system sumcheck and the system proofs.
+// Elsewhere: what prepares or checks a trace before its commitment (fill, sum,
+// scan, sort, lookup counts, shifted extension, public columns, witness check),
+// trace_host.hip; the FRI prover, fri_prover.hip; the sumcheck, PCS and batched-
+// PCS provers above it, pcs_prover.hip; the multi-GPU schedules, sharded.hip, and
+// their rank-local steps, shard_steps.hip; verifiers and host transcript, verify.cpp.
 // Every large vector is device resident; only roots, round sums (32 B each),
 // the last element and the opened query paths cross PCIe.  The whole-proof
 // entries run the Fiat-Shamir transcript on the device (FriDevLoop): the kernel
@@ -35,6 +35,7 @@
 #include "host_sha256.hpp"
 #include "host_transcript.hpp"
 #include "context.hpp"
+#include "cs_call.hpp"
 #include "cs_program.hpp"
 #include "cs_sumcheck.hpp"
 #include "fri_prover.hpp"
@@ -46,13 +47,7 @@
 #include "sumcheck.hpp"
 #include "system_head.hpp"
 #include "tables.hpp"
-#include "trace_check.hpp"
 #include "trace_commit.hpp"
-#include "trace_fill.hpp"
-#include "trace_lookup.hpp"
-#include "trace_public.hpp"
-#include "trace_scan.hpp"
-#include "trace_sort.hpp"
 #include "trace_shift.hpp"
 #include "transcript_dev.hpp"
 
@@ -69,11 +64,6 @@ using namespace mlh;
 // kTablePin stamps -- every table the running operation holds a pointer to --
 // are never evicted.
 constexpr uint64_t kTablePin = 24;
-
-static bool ranges_overlap(const void* a, const void* b, uint64_t bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y ? y - x < bytes : x - y < bytes;
-}
 
 static mlh_status table_make_room(mlh_ctx* ctx, size_t need) {
   if (ctx->table_bytes + need <= ctx->table_limit) return MLH_OK;
@@ -209,11 +199,7 @@ bool mlh::check_generator(u128 gen, uint32_t log_n) {
 // the root of a tree of `leaves` leaves: one synchronising D2H copy (out may be null)
 mlh_status mlh::read_root(mlh_ctx* ctx, const uint8_t* layers, uint64_t leaves, uint8_t out[32]) {
   if (!out) return MLH_OK;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, layers + (2 * leaves - 2) * 32, 32,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(out, ctx->pinned, 32);
-  return MLH_OK;
+  return read_back(ctx, layers + (2 * leaves - 2) * 32, 32, out);
 }
 
 // Fold twiddles gen_pows[len - e] = g^(-e), e < len = 2^log_len (fri/mod.rs:106-110),
@@ -895,10 +881,11 @@ static mlh_status eq_table_impl(mlh_ctx* ctx, const uint8_t* host_points, uint32
   return MLH_OK;
 }
 
-static mlh_status read_pair(mlh_ctx* ctx, const fe* dev2, uint8_t out[32]) {
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev2, 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(out, ctx->pinned, 32);
+// the first of the pair in ctx->small
+static mlh_status read_small_first(mlh_ctx* ctx, uint8_t out[16]) {
+  uint8_t pair[32];
+  MLH_TRY(read_back(ctx, ctx->small, 32, pair));
+  memcpy(out, pair, 16);
   return MLH_OK;
 }
 
@@ -910,10 +897,7 @@ mlh_status mlh_mle_evaluate(mlh_ctx* ctx, const void* dev_evals, uint32_t n,
   MLH_TRY(mlh_eq_table(ctx, host_args, n, eq.p));
   HIP_TRY(ctx, launch_dot(reinterpret_cast<const fe*>(dev_evals), eq.as<fe>(), 1ull << n,
                           ctx->partials, ctx->small, ctx->stream));
-  uint8_t pair[32];
-  MLH_TRY(read_pair(ctx, ctx->small, pair));
-  memcpy(out, pair, 16);
-  return MLH_OK;
+  return read_small_first(ctx, out);
 }
 
 mlh_status mlh_mle_coeffs_evaluate(mlh_ctx* ctx, const void* dev_coeffs, uint32_t n,
@@ -924,10 +908,7 @@ mlh_status mlh_mle_coeffs_evaluate(mlh_ctx* ctx, const void* dev_coeffs, uint32_
   MLH_TRY(eq_table_impl(ctx, host_args, n, mono.p, true));
   HIP_TRY(ctx, launch_dot(reinterpret_cast<const fe*>(dev_coeffs), mono.as<fe>(), 1ull << n,
                           ctx->partials, ctx->small, ctx->stream));
-  uint8_t pair[32];
-  MLH_TRY(read_pair(ctx, ctx->small, pair));
-  memcpy(out, pair, 16);
-  return MLH_OK;
+  return read_small_first(ctx, out);
 }
 
 mlh_status mlh_poly_evaluate(mlh_ctx* ctx, const void* dev_coeffs, uint64_t n, const uint8_t x[16],
@@ -948,10 +929,7 @@ mlh_status mlh_poly_evaluate(mlh_ctx* ctx, const void* dev_coeffs, uint64_t n, c
   HIP_TRY(ctx, launch_pow_table(thi.as<fe>(), to_fe(h_pow(xv, 4096)), to_fe(1), nhi, ctx->stream));
   HIP_TRY(ctx, launch_poly_eval(reinterpret_cast<const fe*>(dev_coeffs), n, tlo.as<fe>(),
                                 thi.as<fe>(), ctx->partials, ctx->small, ctx->stream));
-  uint8_t pair[32];
-  MLH_TRY(read_pair(ctx, ctx->small, pair));
-  memcpy(out, pair, 16);
-  return MLH_OK;
+  return read_small_first(ctx, out);
 }
 
 mlh_status mlh_trace_evaluate(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
@@ -980,7 +958,7 @@ mlh_status mlh_sumcheck_partial_sums(mlh_ctx* ctx, const void* dev_matrix, const
   HIP_TRY(ctx, launch_sums(reinterpret_cast<const fe*>(dev_matrix),
                            reinterpret_cast<const fe*>(dev_delta), 1ull << (log_height - 1),
                            ctx->partials, ctx->small, ctx->stream));
-  return read_pair(ctx, ctx->small, out);
+  return read_back(ctx, ctx->small, 32, out);
 }
 
 mlh_status mlh_sumcheck_fold(mlh_ctx* ctx, void* dev_matrix, void* dev_delta, uint32_t log_height,
@@ -999,12 +977,8 @@ mlh_status mlh_sumcheck_fold_and_sums(mlh_ctx* ctx, void* dev_matrix, void* dev_
   HIP_TRY(ctx, launch_fold_sums(reinterpret_cast<fe*>(dev_matrix), reinterpret_cast<fe*>(dev_delta),
                                 1ull << log_height, to_fe(h_load(r)), ctx->partials, ctx->small,
                                 ctx->stream));
-  return read_pair(ctx, ctx->small, out);
+  return read_back(ctx, ctx->small, 32, out);
 }
-
-}  // extern "C"
-
-extern "C" {
 
 mlh_status mlh_merkle_open(mlh_ctx* ctx, const void* dev_layers, uint64_t leaves,
                            const uint64_t* host_idx, uint32_t nq, uint8_t* out) {
@@ -1027,10 +1001,6 @@ mlh_status mlh_merkle_open(mlh_ctx* ctx, const void* dev_layers, uint64_t leaves
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MLH_OK;
 }
-
-}  // extern "C"
-
-extern "C" {
 
 // ---------------------------------------------------------------------------
 // kernel timer
@@ -1219,477 +1189,21 @@ void mlh_trace_commitment_destroy(mlh_trace_commitment* c) {
   }
 }
 
-// ---- phase 2 of the two-phase proof: fill and column sum (trace_fill.hip) ----
-
-// The fill with an explicit launch shape (mlh_trace_fill: the shape of
-// fill_shape).  One pooled buffer holds this call's randoms beside the
-// program's constants, instruction words and output words, filled by one copy.
-mlh_status mlh_trace_fill_shaped(mlh_ctx* ctx, const mlh_fill_program* prog, void* dev_matrix,
-                                 uint32_t log_height, uint32_t width, const uint8_t* host_randoms,
-                                 uint32_t threads, uint32_t rows_per_thread) {
-  if (!ctx || !prog || !dev_matrix || width != prog->p.width || log_height > kCsMaxLogHeight ||
-      (prog->p.n_randoms && !host_randoms) || !fill_shape_ok(prog->p, threads, rows_per_thread))
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_fill: bad argument");
-  const FillProgram& p = prog->p;
-  std::vector<u128> rnd(p.n_randoms);
-  for (uint32_t i = 0; i < p.n_randoms; ++i)
-    if ((rnd[i] = h_load(host_randoms + 16ull * i)) >= kModulus)
-      return fail(ctx, MLH_ERR_INVALID, "non-canonical random");
-  const FillImageLayout l = fill_image_layout(p);
-  const std::vector<uint8_t> img = fill_build_image(p, rnd.data());
-  PoolBuf buf(ctx);
-  MLH_TRY(buf.alloc(img.size()));
-  HIP_TRY(ctx, hipMemcpyAsync(buf.p, img.data(), img.size(), hipMemcpyHostToDevice, ctx->stream));
-  const uint8_t* b = buf.as<uint8_t>();
-  FillDev dev{};
-  dev.uni = reinterpret_cast<const fe*>(b);
-  dev.code = reinterpret_cast<const uint32_t*>(b + l.code_off);
-  dev.outs = reinterpret_cast<const uint32_t*>(b + l.outs_off);
-  dev.width = p.width;
-  dev.n_temps = p.n_temps;
-  dev.n_instr = p.n_instr;
-  dev.n_pre = p.n_pre;
-  dev.n_inv = p.n_inv;
-  dev.n_outputs = p.n_outputs;
-  dev.K = rows_per_thread;
-  const uint64_t height = 1ull << log_height;
-  const uint32_t blocks = fill_blocks(p, fill_chunks(height, threads, dev.K), threads, dev.K);
-  PoolBuf prefix(ctx);  // the lanes' prefix products (trace_fill.hip)
-  if (const uint64_t elems = blocks * fill_prefix_elems(p, threads, dev.K)) {
-    MLH_TRY(prefix.alloc(16 * elems));
-    dev.prefix = prefix.as<fe>();
-  }
-  ProfScope ps(ctx, "trace_fill");
-  HIP_TRY(ctx, launch_trace_fill(dev, threads, blocks, reinterpret_cast<fe*>(dev_matrix), height,
-                                 ctx->stream));
-  ps.end();
-  return MLH_OK;  // (the buffer goes back to the pool: its next user is behind this launch on the stream)
-}
-
-mlh_status mlh_trace_fill(mlh_ctx* ctx, const mlh_fill_program* prog, void* dev_matrix,
-                          uint32_t log_height, uint32_t width, const uint8_t* host_randoms) {
-  uint32_t B = 0, K = 0;
-  if (prog && log_height <= kCsMaxLogHeight) fill_shape(prog->p, 1ull << log_height, &B, &K);
-  return mlh_trace_fill_shaped(ctx, prog, dev_matrix, log_height, width, host_randoms, B, K);
-}
-
-mlh_status mlh_trace_column_sum(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
-                                uint32_t width, uint32_t column_mask, uint8_t out[16]) {
-  if (!ctx || !dev_matrix || !out || width < 1 || width > kCsMaxWidth ||
-      log_height > kCsMaxLogHeight || (width < 32 && (column_mask >> width)))
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_column_sum: bad argument");
-  ProfScope ps(ctx, "trace_column_sum");
-  HIP_TRY(ctx, launch_trace_column_sum(reinterpret_cast<const fe*>(dev_matrix), 1ull << log_height,
-                                       width, column_mask, ctx->partials, ctx->small, ctx->stream));
-  ps.end();
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, ctx->small, 16, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(out, ctx->pinned, 16);
-  return MLH_OK;
-}
-
-// ---- running sums and running products down columns (trace_scan.hip) ----
-
-static_assert(MLH_SCAN_ADD == kScanAdd && MLH_SCAN_MUL == kScanMul, "mlhip.h and trace_scan.hpp agree");
-
-static bool scan_dims_ok(uint32_t log_height, uint32_t width, uint32_t n_scans) {
-  return log_height <= kCsMaxLogHeight && width >= 1 && width <= kCsMaxWidth && n_scans >= 1 &&
-         n_scans <= kScanMaxScans;
-}
-
-mlh_status mlh_trace_scan_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
-                                 uint32_t width, uint32_t n_scans, const uint8_t* ops,
-                                 const uint8_t* src_columns, const uint8_t* dst_columns,
-                                 const uint8_t* host_inits, uint8_t* totals_out, uint32_t threads,
-                                 uint32_t rows_per_thread, uint32_t max_blocks) {
-  if (!ctx || !dev_matrix || !ops || !src_columns || !dst_columns || !host_inits ||
-      !scan_dims_ok(log_height, width, n_scans) ||
-      !scan_shape_ok(threads, rows_per_thread, max_blocks))
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_scan: bad argument");
-  ScanArgs a{};
-  uint32_t written = 0;
-  for (uint32_t s = 0; s < n_scans; ++s) {
-    if (ops[s] > kScanMul || src_columns[s] >= width || dst_columns[s] >= width ||
-        ((written >> dst_columns[s]) & 1u))
-      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_scan: bad op, column out of range or "
-                                        "destination written twice");
-    written |= 1u << dst_columns[s];
-    const u128 init = h_load(host_inits + 16ull * s);
-    if (init >= kModulus) return fail(ctx, MLH_ERR_INVALID, "mlh_trace_scan: non-canonical init");
-    a.op[s] = ops[s];
-    a.src[s] = src_columns[s];
-    a.dst[s] = dst_columns[s];
-    a.init[s] = to_fe(init);
-  }
-  a.m = reinterpret_cast<fe*>(dev_matrix);
-  a.height = 1ull << log_height;
-  a.width = width;
-  a.n_scans = n_scans;
-  a.rows_per_thread = rows_per_thread;
-  a.tiles = scan_tiles(a.height, threads, rows_per_thread);
-  a.blocks = scan_blocks(a.tiles, max_blocks);
-  a.tiles_per_block = (a.tiles + a.blocks - 1) / a.blocks;
-  PoolBuf scratch(ctx);  // the blocks' aggregates and offsets, the totals
-  MLH_TRY(scratch.alloc(scan_scratch_elems(n_scans, a.blocks) * sizeof(fe)));
-  a.aggregates = scratch.as<fe>();
-  a.offsets = a.aggregates + (size_t)n_scans * a.blocks;
-  a.totals = a.offsets + (size_t)n_scans * a.blocks;
-  ProfScope ps(ctx, "trace_scan");
-  HIP_TRY(ctx, launch_trace_scan(a, threads, ctx->stream));
-  ps.end();
-  if (!totals_out) return MLH_OK;  // (the scratch's next user is behind these launches)
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, a.totals, 16ull * n_scans, hipMemcpyDeviceToHost,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(totals_out, ctx->pinned, 16ull * n_scans);
-  return MLH_OK;
-}
-
-mlh_status mlh_trace_scan(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height, uint32_t width,
-                          uint32_t n_scans, const uint8_t* ops, const uint8_t* src_columns,
-                          const uint8_t* dst_columns, const uint8_t* host_inits,
-                          uint8_t* totals_out) {
-  return mlh_trace_scan_shaped(ctx, dev_matrix, log_height, width, n_scans, ops, src_columns,
-                               dst_columns, host_inits, totals_out, kScanThreads,
-                               kScanRowsPerThread, kScanMaxBlocks);
-}
-
-mlh_status mlh_trace_scan_launch_info(uint32_t log_height, uint32_t width, uint32_t n_scans,
-                                      uint32_t* threads, uint32_t* rows_per_thread,
-                                      uint32_t* blocks) {
-  if (!threads || !rows_per_thread || !blocks || !scan_dims_ok(log_height, width, n_scans))
-    return MLH_ERR_INVALID;
-  *threads = kScanThreads;
-  *rows_per_thread = kScanRowsPerThread;
-  *blocks = scan_blocks(scan_tiles(1ull << log_height, kScanThreads, kScanRowsPerThread),
-                        kScanMaxBlocks);
-  return MLH_OK;
-}
-
-// ---- sorted copies of columns (trace_sort.hip) ----
-
-static_assert(MLH_SORT_MAX_KEYS == kSortMaxKeys && MLH_SORT_MAX_COPIES == kSortMaxCopies &&
-                  MLH_SORT_NO_COLUMN == kSortNoColumn,
-              "mlhip.h and trace_sort.hpp agree");
-
-static bool sort_dims_ok(uint32_t log_height, uint32_t width, uint32_t n_keys) {
-  return log_height <= kSortMaxLogHeight && width >= 1 && width <= kCsMaxWidth && n_keys >= 1 &&
-         n_keys <= kSortMaxKeys;
-}
-
-mlh_status mlh_trace_sort_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
-                                 uint32_t width, uint32_t n_keys, const uint32_t* key_columns,
-                                 uint32_t n_copies, const uint32_t* src_columns,
-                                 const uint32_t* dst_columns, uint32_t perm_column,
-                                 uint32_t* passes_out, uint32_t threads, uint32_t rows_per_thread,
-                                 uint32_t max_blocks, uint32_t flags) {
-  if (!ctx || !dev_matrix || !key_columns || !sort_dims_ok(log_height, width, n_keys) ||
-      n_copies > kSortMaxCopies || (n_copies && (!src_columns || !dst_columns)) ||
-      (!n_copies && perm_column == kSortNoColumn) ||
-      !scan_shape_ok(threads, rows_per_thread, max_blocks) || (flags & ~kSortRunAll))
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: bad argument");
-  SortArgs a{};
-  uint32_t read = 0, written = 0;  // column masks
-  for (uint32_t k = 0; k < n_keys; ++k) {
-    if (key_columns[k] >= width)
-      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: key column out of range");
-    read |= 1u << key_columns[k];
-    a.key[k] = (uint8_t)key_columns[k];
-  }
-  for (uint32_t s = 0; s < n_copies; ++s) {
-    if (src_columns[s] >= width || dst_columns[s] >= width || ((written >> dst_columns[s]) & 1u))
-      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: column out of range or destination "
-                                        "written twice");
-    read |= 1u << src_columns[s];
-    written |= 1u << dst_columns[s];
-    a.src[s] = (uint8_t)src_columns[s];
-    a.dst[s] = (uint8_t)dst_columns[s];
-  }
-  if (perm_column != kSortNoColumn) {
-    if (perm_column >= width || ((written >> perm_column) & 1u))
-      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: perm_column out of range or a destination");
-    written |= 1u << perm_column;
-  }
-  if (read & written)
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_sort: a destination is a key or a source");
-  a.m = reinterpret_cast<fe*>(dev_matrix);
-  a.height = 1ull << log_height;
-  a.width = width;
-  a.n_keys = n_keys;
-  a.n_copies = n_copies;
-  a.perm_column = perm_column;
-  a.threads = threads;
-  a.rows_per_thread = rows_per_thread;
-  a.tiles = scan_tiles(a.height, threads, rows_per_thread);
-  a.blocks = scan_blocks(a.tiles, max_blocks);
-  a.tiles_per_block = (a.tiles + a.blocks - 1) / a.blocks;
-  PoolBuf scratch(ctx);  // the pairs, the census and one pass's tables
-  MLH_TRY(scratch.alloc(sort_scratch_bytes(a.height, n_keys, a.blocks)));
-  sort_carve(a, scratch.p);
-  const uint32_t digits = kSortDigitsPerKey * n_keys;
-  ProfScope ps(ctx, "trace_sort");
-  HIP_TRY(ctx, launch_sort_census(a, ctx->stream));
-  uint64_t run = digits == 64 ? ~0ull : (1ull << digits) - 1;
-  if (!(flags & kSortRunAll)) {  // drop the digits in which all rows agree
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, a.same, 4ull * digits, hipMemcpyDeviceToHost,
-                                ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint32_t same[kSortDigitsPerKey * kSortMaxKeys];
-    memcpy(same, ctx->pinned, 4ull * digits);
-    for (uint32_t g = 0; g < digits; ++g)
-      if (same[g]) run &= ~(1ull << g);
-  }
-  HIP_TRY(ctx, launch_sort_passes(a, run, ctx->stream));
-  ps.end();
-  if (passes_out) *passes_out = (uint32_t)__builtin_popcountll(run);
-  return MLH_OK;  // (the scratch's next user is behind these launches)
-}
-
-mlh_status mlh_trace_sort(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height, uint32_t width,
-                          uint32_t n_keys, const uint32_t* key_columns, uint32_t n_copies,
-                          const uint32_t* src_columns, const uint32_t* dst_columns,
-                          uint32_t perm_column, uint32_t* passes_out) {
-  return mlh_trace_sort_shaped(ctx, dev_matrix, log_height, width, n_keys, key_columns, n_copies,
-                               src_columns, dst_columns, perm_column, passes_out, kSortThreads,
-                               kSortRowsPerThread, kScanMaxBlocks, 0);
-}
-
-mlh_status mlh_trace_sort_launch_info(uint32_t log_height, uint32_t width, uint32_t n_keys,
-                                      uint32_t* threads, uint32_t* rows_per_thread,
-                                      uint32_t* blocks) {
-  if (!threads || !rows_per_thread || !blocks || !sort_dims_ok(log_height, width, n_keys))
-    return MLH_ERR_INVALID;
-  *threads = kSortThreads;
-  *rows_per_thread = kSortRowsPerThread;
-  *blocks = scan_blocks(scan_tiles(1ull << log_height, kSortThreads, kSortRowsPerThread),
-                        kScanMaxBlocks);
-  return MLH_OK;
-}
-
-// ---- a lookup's multiplicities, before the first commitment (trace_lookup.hip) ----
-
-static bool lookup_columns_ok(uint32_t width, uint32_t value_mask, uint32_t T, uint32_t C) {
-  return width >= 1 && width <= kCsMaxWidth && value_mask && (width == 32 || !(value_mask >> width)) &&
-         T < width && C < width && T != C && !((value_mask >> T) & 1u) && !((value_mask >> C) & 1u);
-}
-
-mlh_status mlh_trace_lookup_counts_shaped(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
-                                          uint32_t width, uint32_t value_column_mask,
-                                          uint32_t table_column, uint32_t count_column,
-                                          uint64_t* n_missing, uint64_t* first_missing_row,
-                                          uint32_t log_slots, uint32_t hash_bits,
-                                          uint32_t max_blocks, uint32_t flags) {
-  if (!ctx || !dev_matrix || !n_missing || !first_missing_row || log_height > kLkMaxLogHeight ||
-      !lookup_columns_ok(width, value_column_mask, table_column, count_column) ||
-      log_slots < log_height || log_slots > kLkMaxLogSlots || hash_bits > log_slots ||
-      (flags & ~kLkNoAggregate))
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_lookup_counts: bad argument");
-  PoolBuf scratch(ctx);  // the counters and the slot array
-  MLH_TRY(scratch.alloc(lk_scratch_bytes(log_slots)));
-  LookupArgs a{};
-  a.m = reinterpret_cast<fe*>(dev_matrix);
-  a.log_height = log_height;
-  a.width = width;
-  a.value_mask = value_column_mask;
-  a.table_column = table_column;
-  a.count_column = count_column;
-  a.log_slots = log_slots;
-  a.hash_bits = hash_bits;
-  a.max_blocks = max_blocks;
-  a.flags = flags;
-  ProfScope ps(ctx, "trace_lookup_counts");
-  HIP_TRY(ctx, launch_lookup_insert(a, scratch.p, ctx->stream));
-  HIP_TRY(ctx, launch_lookup_count(a, ctx->stream));
-  ps.end();
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, a.counters, sizeof(LookupCounters),
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  LookupCounters c;
-  memcpy(&c, ctx->pinned, sizeof(c));
-  *n_missing = c.n_missing;
-  *first_missing_row = c.first_missing_row == kLkEmpty ? UINT64_MAX : c.first_missing_row;
-  return MLH_OK;
-}
-
-mlh_status mlh_trace_lookup_counts(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
-                                   uint32_t width, uint32_t value_column_mask,
-                                   uint32_t table_column, uint32_t count_column,
-                                   uint64_t* n_missing, uint64_t* first_missing_row) {
-  const uint32_t log_slots = lk_default_log_slots(log_height);
-  return mlh_trace_lookup_counts_shaped(ctx, dev_matrix, log_height, width, value_column_mask,
-                                        table_column, count_column, n_missing, first_missing_row,
-                                        log_slots, log_slots, 0, 0);
-}
-
-mlh_status mlh_trace_lookup_counts_launch_info(uint32_t log_height, uint32_t n_value_columns,
-                                               uint32_t* threads, uint32_t* blocks,
-                                               uint32_t* log_slots) {
-  if (!threads || !blocks || !log_slots || log_height > kLkMaxLogHeight || n_value_columns < 1 ||
-      n_value_columns > kCsMaxWidth - 2)
-    return MLH_ERR_INVALID;
-  *threads = kLkThreads;
-  *blocks = lk_blocks((uint64_t)n_value_columns << log_height, 0);
-  *log_slots = lk_default_log_slots(log_height);
-  return MLH_OK;
-}
-
-// ---- the same for tuple keys ----
-
-static_assert(MLH_LOOKUP_MAX_ARITY == kLkMaxArity && MLH_LOOKUP_MAX_TUPLES == kLkMaxTuples &&
-                  MLH_LOOKUP_NO_SELECTOR == kLkNoSelector,
-              "mlhip.h and trace_lookup.hpp agree");
-
-// Checks the column lists and copies them into a (table columns) and lists.
-static bool lookup_tuple_columns_ok(uint32_t width, uint32_t arity, const uint32_t* table,
-                                    uint32_t n_tuples, const uint32_t* values,
-                                    const uint32_t* selectors, uint32_t C, LookupTupleArgs& a,
-                                    LookupTupleLists& lists) {
-  if (!table || !values || width < 1 || width > kCsMaxWidth || arity < 1 || arity > kLkMaxArity ||
-      n_tuples < 1 || n_tuples > kLkMaxTuples || arity * n_tuples > kLkMaxTupleColumns || C >= width)
-    return false;
-  uint32_t tmask = 0;
-  for (uint32_t c = 0; c < arity; ++c) {
-    if (table[c] >= width || table[c] == C || ((tmask >> table[c]) & 1u)) return false;
-    tmask |= 1u << table[c];
-    a.table_columns[c] = table[c];
-  }
-  for (uint32_t k = 0; k < arity * n_tuples; ++k) {
-    if (values[k] >= width || values[k] == C || ((tmask >> values[k]) & 1u)) return false;
-    lists.value_columns[k] = values[k];
-  }
-  for (uint32_t l = 0; l < n_tuples; ++l) {
-    const uint32_t s = selectors ? selectors[l] : kLkNoSelector;
-    if (s != kLkNoSelector && (s >= width || s == C)) return false;
-    lists.selector_columns[l] = s;
-  }
-  return true;
-}
-
-mlh_status mlh_trace_lookup_tuple_counts_shaped(mlh_ctx* ctx, void* dev_matrix,
-                                                uint32_t log_height, uint32_t width,
-                                                uint32_t arity, const uint32_t* table_columns,
-                                                uint32_t n_tuples, const uint32_t* value_columns,
-                                                const uint32_t* selector_columns,
-                                                uint32_t count_column, uint64_t* n_missing,
-                                                uint64_t* first_missing_row, uint32_t log_slots,
-                                                uint32_t hash_bits, uint32_t max_blocks,
-                                                uint32_t flags) {
-  LookupTupleArgs a{};
-  LookupTupleLists lists{};
-  if (!ctx || !dev_matrix || !n_missing || !first_missing_row || log_height > kLkMaxLogHeight ||
-      !lookup_tuple_columns_ok(width, arity, table_columns, n_tuples, value_columns,
-                               selector_columns, count_column, a, lists) ||
-      log_slots < log_height || log_slots > kLkMaxLogSlots || hash_bits > log_slots ||
-      (flags & ~kLkNoAggregate))
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_lookup_tuple_counts: bad argument");
-  PoolBuf scratch(ctx);  // the counters, the column lists and the slot array
-  MLH_TRY(scratch.alloc(lk_scratch_bytes(log_slots)));
-  a.m = reinterpret_cast<fe*>(dev_matrix);
-  a.log_height = log_height;
-  a.width = width;
-  a.arity = arity;
-  a.n_tuples = n_tuples;
-  a.count_column = count_column;
-  a.log_slots = log_slots;
-  a.hash_bits = hash_bits;
-  a.max_blocks = max_blocks;
-  a.flags = flags;
-  ProfScope ps(ctx, "trace_lookup_tuple_counts");
-  HIP_TRY(ctx, launch_lookup_tuple_insert(a, lists, scratch.p, ctx->stream));
-  HIP_TRY(ctx, launch_lookup_tuple_count(a, ctx->stream));
-  ps.end();
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, a.counters, sizeof(LookupCounters),
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  LookupCounters c;
-  memcpy(&c, ctx->pinned, sizeof(c));
-  *n_missing = c.n_missing;
-  *first_missing_row = c.first_missing_row == kLkEmpty ? UINT64_MAX : c.first_missing_row;
-  return MLH_OK;
-}
-
-mlh_status mlh_trace_lookup_tuple_counts(mlh_ctx* ctx, void* dev_matrix, uint32_t log_height,
-                                         uint32_t width, uint32_t arity,
-                                         const uint32_t* table_columns, uint32_t n_tuples,
-                                         const uint32_t* value_columns,
-                                         const uint32_t* selector_columns, uint32_t count_column,
-                                         uint64_t* n_missing, uint64_t* first_missing_row) {
-  const uint32_t log_slots = lk_default_log_slots(log_height);
-  return mlh_trace_lookup_tuple_counts_shaped(ctx, dev_matrix, log_height, width, arity,
-                                              table_columns, n_tuples, value_columns,
-                                              selector_columns, count_column, n_missing,
-                                              first_missing_row, log_slots, log_slots, 0, 0);
-}
-
-mlh_status mlh_trace_lookup_tuple_counts_launch_info(uint32_t log_height, uint32_t n_tuples,
-                                                     uint32_t* threads, uint32_t* blocks,
-                                                     uint32_t* log_slots) {
-  if (!threads || !blocks || !log_slots || log_height > kLkMaxLogHeight || n_tuples < 1 ||
-      n_tuples > kLkMaxTuples)
-    return MLH_ERR_INVALID;
-  *threads = kLkThreads;
-  *blocks = lk_blocks((uint64_t)n_tuples << log_height, 0);
-  *log_slots = lk_default_log_slots(log_height);
-  return MLH_OK;
-}
-
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
 // constraint-system sumcheck (constraint_system/sumcheck.rs:40-53,147-247):
 // width-W tables, the composition a constraint program (cs_program.hpp)
 // ---------------------------------------------------------------------------
-// One call's device image of a program: the uniform pool (this call's randoms
-// and mask beside the program's constants), the interpolation matrix and the
-// instruction words, in one pooled buffer filled by one copy.
-struct CsCall {
-  PoolBuf buf;
-  std::vector<uint8_t> img;  // (kept until the call's sync: the copy's source)
-  CsDev dev{};
-  const fe* vinv = nullptr;
-  uint32_t threads = 0;
-  explicit CsCall(mlh_ctx* c) : buf(c) {}
-  mlh_status init(mlh_ctx* ctx, const mlh_cs_program* prog, const uint8_t* host_randoms,
-                  const uint8_t* host_mask) {
-    const CsProgram& p = prog->p;
-    std::vector<u128> rnd(p.n_randoms), mask(p.n_constraints);
-    for (uint32_t i = 0; i < p.n_randoms; ++i)
-      if ((rnd[i] = h_load(host_randoms + 16ull * i)) >= kModulus)
-        return fail(ctx, MLH_ERR_INVALID, "non-canonical random");
-    for (uint32_t i = 0; i < p.n_constraints; ++i)
-      if ((mask[i] = h_load(host_mask + 16ull * i)) >= kModulus)
-        return fail(ctx, MLH_ERR_INVALID, "non-canonical mask");
-    const CsImageLayout l = cs_image_layout(p);
-    img = cs_build_image(p, rnd.data(), mask.data());
-    MLH_TRY(buf.alloc(l.bytes));
-    HIP_TRY(ctx, hipMemcpyAsync(buf.p, img.data(), l.bytes, hipMemcpyHostToDevice, ctx->stream));
-    const uint8_t* b = buf.as<uint8_t>();
-    dev.uni = reinterpret_cast<const fe*>(b);
-    dev.code = reinterpret_cast<const uint32_t*>(b + l.code_off);
-    dev.outs = reinterpret_cast<const uint32_t*>(b + l.outs_off);
-    dev.width = p.width;
-    dev.n_temps = p.n_temps;
-    dev.n_instr = p.n_instr;
-    dev.n_constraints = p.n_constraints;
-    dev.D = p.points();
-    vinv = dev.uni + l.vinv_off;
-    threads = cs_threads(cs_slots(p));
-    return MLH_OK;
-  }
-};
-
 static bool cs_args_ok(const mlh_cs_program* prog, uint32_t width, const void* m, const void* d,
                        const uint8_t* randoms, const uint8_t* mask) {
   return prog && m && d && mask && width == prog->p.width && (!prog->p.n_randoms || randoms);
 }
 
 static mlh_status cs_read_sums(mlh_ctx* ctx, const CsCall& cc, uint32_t nb, uint8_t* out) {
+  static_assert(16 * (kCsMaxDegree + 2) <= kPinnedBytes, "a round's sums fit the staging buffer");
   HIP_TRY(ctx, launch_cs_reduce(ctx->partials, nb, cc.dev.D, ctx->small, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, ctx->small, 16ull * cc.dev.D, hipMemcpyDeviceToHost,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(out, ctx->pinned, 16ull * cc.dev.D);
-  return MLH_OK;
+  return read_back(ctx, ctx->small, 16ull * cc.dev.D, out);
 }
 
 extern "C" {
@@ -1875,10 +1389,9 @@ static mlh_status system_prove_core(mlh_ctx* ctx, const mlh_cs_program* prog,
                                        polys_out, rs.data()));
     ps.end();
   }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev_matrix, 16ull * W, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<uint8_t> output(ctx->pinned, ctx->pinned + 16ull * W);
-  std::vector<uint8_t> rs2(16ull * L), output2;
+  static_assert(16 * kCsMaxWidth <= kPinnedBytes, "a row of the trace fits the staging buffer");
+  std::vector<uint8_t> output(16ull * W), rs2(16ull * L), output2;
+  MLH_TRY(read_back(ctx, dev_matrix, output.size(), output.data()));
   if (sh) {  // step 7: sum_j succ_rs[j] sum_k lambda^k T_{c_k}[j] = sum_k lambda^k N_k
     ProfScope ps(ctx, "system_shift_sumcheck");
     const uint32_t Wt = W - sh->K;
@@ -1894,10 +1407,8 @@ static mlh_status system_prove_core(mlh_ctx* ctx, const mlh_cs_program* prog,
                                   ctx->stream));
     MLH_TRY(mlh_cs_sumcheck_prove(ctx, &sp, Wt, sh->dev_copy, sh->dev_succ, L, lambdas.data(), one,
                                   claim2, tr, sh->polys_out, rs2.data()));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, sh->dev_copy, 16ull * Wt, hipMemcpyDeviceToHost,
-                                ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    output2.assign(ctx->pinned, ctx->pinned + 16ull * Wt);
+    output2.resize(16ull * Wt);
+    MLH_TRY(read_back(ctx, sh->dev_copy, output2.size(), output2.data()));
     ps.end();
   }
   {
@@ -1983,80 +1494,6 @@ mlh_status mlh_system_prove_phased(mlh_ctx* ctx, const mlh_cs_program* prog,
   return MLH_OK;
 }
 
-// ---- shifted columns (trace_shift.hip; mlhip.h gives the protocol) -------------
-mlh_status mlh_trace_extend_next(mlh_ctx* ctx, const void* dev_matrix, uint32_t log_height,
-                                 uint32_t width, const uint32_t* shift_columns, uint32_t n_shifts,
-                                 void* dev_out) {
-  if (!ctx || !dev_matrix || !dev_out || (n_shifts && !shift_columns))
-    return fail(ctx, MLH_ERR_INVALID, "null argument");
-  if (width < 1 || n_shifts > kTsMaxWidth || width + n_shifts > kTsMaxWidth ||
-      log_height > kCsMaxLogHeight)
-    return fail(ctx, MLH_ERR_INVALID, "width + n_shifts 1..32, log_height 0..32");
-  for (uint32_t k = 0; k < n_shifts; ++k)
-    if (shift_columns[k] >= width) return fail(ctx, MLH_ERR_INVALID, "source column outside the trace");
-  const uint64_t in_bytes = (16ull * width) << log_height;
-  const uint64_t out_bytes = (16ull * (width + n_shifts)) << log_height;
-  if (ranges_overlap(dev_matrix, dev_out, (uintptr_t)dev_matrix < (uintptr_t)dev_out ? in_bytes : out_bytes))
-    return fail(ctx, MLH_ERR_INVALID, "the extension is out of place: the buffers overlap");
-  ProfScope ps(ctx, "trace_extend_next");
-  HIP_TRY(ctx, launch_trace_extend_next(reinterpret_cast<const fe*>(dev_matrix),
-                                        reinterpret_cast<fe*>(dev_out), log_height, width,
-                                        shift_columns, n_shifts, ctx->stream));
-  ps.end();
-  return MLH_OK;
-}
-
-mlh_status mlh_trace_extend_next_launch_info(uint32_t log_height, uint32_t width, uint32_t n_shifts,
-                                             uint32_t* tile_rows, uint32_t* blocks) {
-  if (!tile_rows || !blocks || width < 1 || n_shifts > kTsMaxWidth ||
-      width + n_shifts > kTsMaxWidth || log_height > kCsMaxLogHeight)
-    return MLH_ERR_INVALID;
-  *tile_rows = 1u << ts_log_rows(log_height, width + n_shifts);
-  *blocks = ts_blocks(log_height, width + n_shifts);
-  return MLH_OK;
-}
-
-mlh_status mlh_eq_table_rotate(mlh_ctx* ctx, const void* dev_in, uint32_t log_n, void* dev_out) {
-  if (!ctx || !dev_in || !dev_out || log_n > 32) return fail(ctx, MLH_ERR_INVALID, "bad argument");
-  if (ranges_overlap(dev_in, dev_out, 16ull << log_n))
-    return fail(ctx, MLH_ERR_INVALID, "the rotation is out of place: the buffers overlap");
-  ProfScope ps(ctx, "eq_rotate");
-  HIP_TRY(ctx, launch_eq_rotate(reinterpret_cast<const fe*>(dev_in), reinterpret_cast<fe*>(dev_out),
-                                log_n, ctx->stream));
-  ps.end();
-  return MLH_OK;
-}
-
-// ---- public columns (trace_public.hip; mlhip.h gives the format and the protocol) ----
-mlh_status mlh_trace_fill_public(mlh_ctx* ctx, const mlh_public_columns* spec, void* dev_matrix,
-                                 uint32_t log_height, uint32_t width) {
-  if (!ctx || !spec || !dev_matrix) return fail(ctx, MLH_ERR_INVALID, "null argument");
-  const PublicColumns& s = spec->p;
-  if (width < 1 || width > kTpMaxWidth || s.count() > width || log_height > kCsMaxLogHeight)
-    return fail(ctx, MLH_ERR_INVALID, "width 1..32, at most width public columns, log_height 0..32");
-  if (!s.fits(log_height))
-    return fail(ctx, MLH_ERR_INVALID, "a period or a sparse row of the spec is beyond the height");
-  PoolBuf img(ctx);
-  MLH_TRY(img.alloc(s.image.size()));
-  HIP_TRY(ctx, hipMemcpyAsync(img.p, s.image.data(), s.image.size(), hipMemcpyHostToDevice,
-                              ctx->stream));
-  ProfScope ps(ctx, "trace_fill_public");
-  HIP_TRY(ctx, launch_trace_fill_public(reinterpret_cast<fe*>(dev_matrix), img.p, s.count(),
-                                        s.sparse_off, s.n_sparse, log_height, width, ctx->stream));
-  ps.end();
-  return MLH_OK;  // (the image goes back to the pool: its next user is behind these launches on the stream)
-}
-
-mlh_status mlh_trace_fill_public_launch_info(uint32_t log_height, uint32_t width, uint32_t n_public,
-                                             uint32_t* tile_rows, uint32_t* blocks) {
-  if (!tile_rows || !blocks || width < 1 || width > kTpMaxWidth || n_public < 1 ||
-      n_public > kPcMaxColumns || n_public > width || log_height > kCsMaxLogHeight)
-    return MLH_ERR_INVALID;
-  *tile_rows = 1u << tp_log_rows(log_height, n_public);
-  *blocks = tp_blocks(log_height, n_public);
-  return MLH_OK;
-}
-
 mlh_status mlh_system_prove_public(mlh_ctx* ctx, const mlh_cs_program* prog,
                                    const mlh_trace_commitment* com1,
                                    const mlh_trace_commitment* com2, uint32_t sum_column_mask,
@@ -2126,153 +1563,6 @@ mlh_status mlh_system_prove_shifted(mlh_ctx* ctx, const mlh_cs_program* prog,
                                     mlh_shifted_proof* proof) {
   return mlh_system_prove_public(ctx, prog, com1, com2, sum_column_mask, shift_columns, n_shifts,
                                  nullptr, dev_matrix, sum, column_sum, tr, proof);
-}
-
-}  // extern "C"
-
-// ---- the witness check (trace_check.hip, trace_public.hip; mlhip.h gives the semantics) ----
-
-// Zeroes the counts and the row count and sets the first rows to all ones,
-// behind the pool's poison fill on the stream (tk_counter_words' layout).
-static mlh_status check_counters_init(mlh_ctx* ctx, PoolBuf& buf, uint32_t n) {
-  MLH_TRY(buf.alloc(8 * tk_counter_words(n)));
-  uint8_t* p = buf.as<uint8_t>();
-  HIP_TRY(ctx, hipMemsetAsync(p, 0, 8ull * (n + 1), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(p + 8ull * (n + 1), 0xFF, 8ull * n, ctx->stream));
-  return MLH_OK;
-}
-
-// The one wait of a check: the counters to the host; counts / first rows to
-// the caller's arrays where given.  -> the rows with any failure and the first
-// rows (n of them, in `firsts`).
-static mlh_status check_counters_read(mlh_ctx* ctx, const PoolBuf& buf, uint32_t n,
-                                      uint64_t* counts_out, uint64_t* first_rows_out,
-                                      uint64_t* n_bad, std::vector<uint64_t>& firsts) {
-  const size_t bytes = 8 * tk_counter_words(n);
-  static_assert(8 * (2 * kCsMaxConstraints + 1) <= kPinnedBytes, "the counters fit the staging buffer");
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, buf.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<uint64_t> w(tk_counter_words(n));
-  memcpy(w.data(), ctx->pinned, bytes);
-  firsts.assign(w.begin() + n + 1, w.end());
-  if (counts_out) memcpy(counts_out, w.data(), 8ull * n);
-  if (first_rows_out) memcpy(first_rows_out, firsts.data(), 8ull * n);
-  *n_bad = w[n];
-  return MLH_OK;
-}
-
-static mlh_status trace_check_run(mlh_ctx* ctx, const mlh_cs_program* prog, const void* dev_matrix,
-                                  uint32_t log_height, uint32_t width, const uint32_t* shift_columns,
-                                  uint32_t n_shifts, const uint8_t* host_randoms,
-                                  uint64_t* counts_out, uint64_t* first_rows_out,
-                                  mlh_trace_check_report* report, bool shaped, uint32_t threads,
-                                  uint32_t max_blocks) {
-  if (!ctx || !prog || !dev_matrix || !report || (n_shifts && !shift_columns))
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check: null argument");
-  const CsProgram& p = prog->p;
-  if (width < 1 || width > kCsMaxWidth || n_shifts > kCsMaxWidth || width + n_shifts != p.width ||
-      log_height > kCsMaxLogHeight)
-    return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check: width 1..32, width + n_shifts the program's "
-                                      "width (at most 32), log_height 0..32");
-  for (uint32_t k = 0; k < n_shifts; ++k)
-    if (shift_columns[k] >= width)
-      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check: source column outside the trace");
-  if (p.n_randoms && !host_randoms) return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check: randoms missing");
-  const uint64_t H = 1ull << log_height;
-  uint32_t blocks;
-  if (shaped) {
-    if (!tk_shape_ok(tk_slots(p), threads, max_blocks))
-      return fail(ctx, MLH_ERR_INVALID, "mlh_trace_check_shaped: threads 64, 128 or 256 whose slots "
-                                        "fit 152 KiB of LDS, max_blocks 1..1024");
-    blocks = tk_blocks_shaped(H, threads, max_blocks);
-  } else {
-    threads = cs_threads(tk_slots(p));
-    blocks = tk_blocks(H, threads);
-  }
-  const uint32_t NC = p.n_constraints;
-  const std::vector<uint8_t> no_mask(16ull * NC, 0);  // (the mask plays no part: its pool entries are zero)
-  CsCall cc(ctx);
-  MLH_TRY(cc.init(ctx, prog, host_randoms, no_mask.data()));  // (checks the randoms before it enqueues)
-  PoolBuf counters(ctx);
-  MLH_TRY(check_counters_init(ctx, counters, NC));
-  ProfScope ps(ctx, "trace_check");
-  HIP_TRY(ctx, launch_trace_check(cc.dev, reinterpret_cast<const fe*>(dev_matrix), log_height, width,
-                                  shift_columns, n_shifts, counters.as<uint64_t>(), threads, blocks,
-                                  ctx->stream));
-  ps.end();
-  std::vector<uint64_t> firsts;
-  uint64_t n_bad = 0;
-  MLH_TRY(check_counters_read(ctx, counters, NC, counts_out, first_rows_out, &n_bad, firsts));
-  report->n_bad_rows = n_bad;
-  report->first_bad_row = UINT64_MAX;
-  report->first_bad_constraint = UINT32_MAX;
-  report->reserved = 0;
-  for (uint32_t c = 0; c < NC; ++c)
-    if (firsts[c] < report->first_bad_row) {
-      report->first_bad_row = firsts[c];
-      report->first_bad_constraint = c;
-    }
-  return MLH_OK;
-}
-
-extern "C" {
-
-mlh_status mlh_trace_check(mlh_ctx* ctx, const mlh_cs_program* prog, const void* dev_matrix,
-                           uint32_t log_height, uint32_t width, const uint32_t* shift_columns,
-                           uint32_t n_shifts, const uint8_t* host_randoms, uint64_t* counts_out,
-                           uint64_t* first_rows_out, mlh_trace_check_report* report) {
-  return trace_check_run(ctx, prog, dev_matrix, log_height, width, shift_columns, n_shifts,
-                         host_randoms, counts_out, first_rows_out, report, false, 0, 0);
-}
-
-mlh_status mlh_trace_check_shaped(mlh_ctx* ctx, const mlh_cs_program* prog, const void* dev_matrix,
-                                  uint32_t log_height, uint32_t width,
-                                  const uint32_t* shift_columns, uint32_t n_shifts,
-                                  const uint8_t* host_randoms, uint64_t* counts_out,
-                                  uint64_t* first_rows_out, mlh_trace_check_report* report,
-                                  uint32_t threads, uint32_t max_blocks) {
-  return trace_check_run(ctx, prog, dev_matrix, log_height, width, shift_columns, n_shifts,
-                         host_randoms, counts_out, first_rows_out, report, true, threads, max_blocks);
-}
-
-mlh_status mlh_trace_check_launch_info(const mlh_cs_program* prog, uint32_t log_height,
-                                       uint32_t* threads, uint32_t* blocks) {
-  if (!prog || !threads || !blocks || log_height > kCsMaxLogHeight) return MLH_ERR_INVALID;
-  *threads = cs_threads(tk_slots(prog->p));
-  *blocks = tk_blocks(1ull << log_height, *threads);
-  return MLH_OK;
-}
-
-mlh_status mlh_trace_check_public(mlh_ctx* ctx, const mlh_public_columns* spec,
-                                  const void* dev_matrix, uint32_t log_height, uint32_t width,
-                                  uint64_t* counts_out, uint64_t* first_rows_out,
-                                  uint64_t* n_bad_rows, uint64_t* first_bad_row) {
-  if (!ctx || !spec || !dev_matrix || !n_bad_rows || !first_bad_row)
-    return fail(ctx, MLH_ERR_INVALID, "null argument");
-  const PublicColumns& s = spec->p;
-  if (width < 1 || width > kTpMaxWidth || s.count() > width || log_height > kCsMaxLogHeight)
-    return fail(ctx, MLH_ERR_INVALID, "width 1..32, at most width public columns, log_height 0..32");
-  if (!s.fits(log_height))
-    return fail(ctx, MLH_ERR_INVALID, "a period or a sparse row of the spec is beyond the height");
-  const uint32_t F = s.count();
-  PoolBuf img(ctx), counters(ctx);
-  MLH_TRY(img.alloc(s.image.size()));
-  HIP_TRY(ctx, hipMemcpyAsync(img.p, s.image.data(), s.image.size(), hipMemcpyHostToDevice,
-                              ctx->stream));
-  MLH_TRY(check_counters_init(ctx, counters, F));
-  ProfScope ps(ctx, "trace_check_public");
-  HIP_TRY(ctx, launch_trace_check_public(reinterpret_cast<const fe*>(dev_matrix), img.p, F,
-                                         s.sparse_off, log_height, width, counters.as<uint64_t>(),
-                                         ctx->stream));
-  ps.end();
-  std::vector<uint64_t> firsts;
-  uint64_t n_bad = 0;
-  MLH_TRY(check_counters_read(ctx, counters, F, counts_out, first_rows_out, &n_bad, firsts));
-  *n_bad_rows = n_bad;
-  *first_bad_row = UINT64_MAX;
-  for (uint64_t f : firsts)
-    if (f < *first_bad_row) *first_bad_row = f;
-  return MLH_OK;
 }
 
 }  // extern "C"

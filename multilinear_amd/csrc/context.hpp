@@ -1,8 +1,8 @@
 // Internal state of an mlh_ctx and the helpers every host-side translation
-// unit of libmlhip shares (capi.hip: the single-GPU C ABI; fri_prover.hip and
-// pcs_prover.hip: the provers above it; sharded.hip: the multi-GPU
-// orchestration; shard_steps.hip: its rank-local steps): the device memory
-// pool, the table cache record, error reporting.  Not part of the public C ABI.
+// unit of libmlhip shares (capi.hip, trace_host.hip: the single-GPU C ABI;
+// fri_prover.hip and pcs_prover.hip: the provers above it; sharded.hip: the
+// multi-GPU orchestration; shard_steps.hip: its rank-local steps): the device
+// memory pool, the table cache record, read-back, error reporting.  Not public.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -266,6 +266,20 @@ struct StreamSwap {
     mlh_status s_ = (expr);        \
     if (s_ != MLH_OK) return s_;   \
   } while (0)
+
+inline bool ranges_overlap(const void* a, const void* b, uint64_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y ? y - x < bytes : x - y < bytes;
+}
+
+// `bytes` (at most kPinnedBytes) from the device to the host: a copy to the
+// start of the pinned staging buffer, the stream's sync, a memcpy out of it.
+static inline mlh_status read_back(mlh_ctx* ctx, const void* dev_src, size_t bytes, void* host_dst) {
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->pinned, dev_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(host_dst, ctx->pinned, bytes);
+  return MLH_OK;
+}
 
 inline mlh::fe to_fe(u128 v) {
   fe r;

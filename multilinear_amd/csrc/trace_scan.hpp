@@ -28,6 +28,16 @@ static inline uint64_t scan_tiles(uint64_t height, uint32_t threads, uint32_t ro
 static inline uint32_t scan_blocks(uint64_t tiles, uint32_t max_blocks) {
   return tiles < max_blocks ? (uint32_t)tiles : max_blocks;
 }
+// Both, and the tiles each block owns, where asked for.  -> the blocks
+static inline uint32_t scan_tiling(uint64_t height, uint32_t threads, uint32_t rows_per_thread,
+                                   uint32_t max_blocks, uint64_t* tiles = nullptr,
+                                   uint64_t* tiles_per_block = nullptr) {
+  const uint64_t t = scan_tiles(height, threads, rows_per_thread);
+  const uint32_t blocks = scan_blocks(t, max_blocks);
+  if (tiles) *tiles = t;
+  if (tiles_per_block) *tiles_per_block = (t + blocks - 1) / blocks;
+  return blocks;
+}
 
 // One call's scans, by value (every index into the arrays is a compile-time
 // constant in the kernels: no private segment).
